@@ -10,6 +10,17 @@ With N > 1 GPUs (torch.distributed, one rank per GPU) the graph grows to 6N+2 ke
 edges sharded by source keyframe (weak scaling, `value` in G8-sized updates per second); the
 rendered frame is split N ways.  Prints ONE JSON line (see the driver contract in the task
 statement).
+
+A plain run does what the headline figure needs: set-up, warm-up, the soak, the timed steps and their
+checks.  Everything else the line can carry (burst and sustained figures, the 40x80 graph, the frontend
+configuration, the sequences, the strong-scaling graph, the exchange step, the rooflines, rendered
+rays/sec, the training batch and the CPU baseline) is measured with `--full`:
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+
+`--dump-outputs DIR` writes the state the last timed step left (poses, disparities, upsampled
+disparities, DSPO scale / shift, BA targets and weights, a seeded sample of the GRU hidden state) as
+DIR/<name>.npy in float32, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -355,6 +366,41 @@ def cpu_baseline_subprocess(timeout=600):
     return json.loads(lines[-1])
 
 
+DUMP_MAX_ELEMS = 1 << 22    # larger arrays are dumped as a seeded sample of DUMP_SAMPLE elements: <= 64 MB in all
+DUMP_SAMPLE = 1 << 21
+
+
+def dump_outputs(out_dir, video, graph, K, rank):
+    """the state the last timed step left, as a caller of FactorGraph.update receives it: the poses, disparities,
+    upsampled disparities and DSPO scale / shift of the K keyframes, and the BA targets, weights and GRU hidden state
+    of this rank's edges.  float32, one DIR/<name>.npy each; an array of more than DUMP_MAX_ELEMS elements is written
+    as <name>_sample.npy, its elements at DUMP_SAMPLE sorted indices drawn with a fixed seed.  Collective when the
+    video is sharded (the upsampled rows of the other ranks are fetched); rank 0 writes."""
+    arrays = {"poses": video.poses[:K], "disps": video.disps[:K], "disps_up": video.fresh_disps_up()[:K],
+              "depth_scale": video.depth_scale[:K], "depth_shift": video.depth_shift[:K],
+              "target": graph.target, "weight": graph.weight, "net": graph.net}
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, x in arrays.items():
+        x = x.detach().float()
+        if x.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, x.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            x, name = x.reshape(-1)[idx.to(x.device)], name + "_sample"
+        a = x.cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
+def _emit(out, rank, world):
+    if rank == 0:
+        print(json.dumps(out))
+    if world > 1:
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,6 +418,10 @@ def main():
     ap.add_argument("--g8-only", action="store_true",
                     help="only the G8 / 640x480 workloads (no 40x80 graph, no frontend configuration, no sequences, no strong-scaling "
                          "graph): what tools/final_profile.sh profiles, so that a kernel's average in the stats is a G8 figure")
+    ap.add_argument("--full", action="store_true",
+                    help="measure every side figure of the line as well (see the module docstring); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline_step()))
@@ -465,11 +515,12 @@ def main():
         return dt
 
     # `value` is measured on a WARM chip: K steps straight after the warm-up run on boost clocks (a 20-step burst is 20 ms),
-    # which no tracking session sustains.  The burst figure is kept as `burst_value`; then `soak` untimed steps bring the
+    # which no tracking session sustains.  The burst figure is kept as `burst_value` (--full); then `soak` untimed steps bring the
     # part to the clocks it holds under this load and the K timed steps of the contract follow.
-    fb_burst0 = int(video.stage2_fallbacks)
-    burst_elapsed = timed_steps(args.steps)
-    fallbacks_burst = int(video.stage2_fallbacks) - fb_burst0
+    if args.full:
+        fb_burst0 = int(video.stage2_fallbacks)
+        burst_elapsed = timed_steps(args.steps)
+        fallbacks_burst = int(video.stage2_fallbacks) - fb_burst0
     soak_steps = int(args.soak)
     for _ in range(soak_steps):
         step()
@@ -490,6 +541,39 @@ def main():
     assert bool(torch.isfinite(graph.target).all()) and bool(torch.isfinite(graph.net.float()).all())
     assert not torch.equal(video.poses[1:K], poses0[1:K]), "the timed steps did not move the poses"
     stage2_steps = (args.steps // 2)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, video, graph, K, rank)
+    N = graph.ii.shape[0]
+    HW = graph.ht * graph.wd
+    out = {
+        "metric": "DSPO BA-update iters/sec + rendered rays/sec, 640x480 Replica keyframe graph",
+        "value": world * args.steps / elapsed,
+        "unit": "BA-update iters/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "soak_steps": soak_steps,
+        "checks": {"ba_status": ba_st, "stage2_fallbacks_timed": fallbacks_timed, "stage2_steps": stage2_steps,
+                   "state_reset_after_soak": True, "state_finite": True},
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f16 corr/ConvGRU, f32 Jacobians, f64 solve; render: f32 (decoder matmuls as 3-term f16 splits, f32 accumulate)", "data": "synthetic",
+        "config": {"workload": (f"G8: 8 keyframes, 36 edges, 60x80 (640x480/8), BA itrs=2, DSPO stages alternating, "
+                                 f"context part of the GRU gates (one map per source keyframe) re-evaluated for all keyframes every 12 steps"
+                                if world == 1 else
+                                f"G8 topology over {K_graph} keyframes = {len(g['ii'])} edges (36 per GPU), 60x80, BA itrs=2, "
+                                f"DSPO stages alternating; value = G8-sized (36-edge) updates per second")
+                               + "; multiview_filter.thresh = 0.25 (reference ships 0.01, configs/mono_point_slam.yaml:75: with "
+                                 "untrained weights 0.01 rejects > 80 % of every frame and no depth_scale step would reach stage 2)"
+                               + "; render: 524k-point cloud, one 640x480 view, 10 samples/ray",
+                   "edges_local": int(N), "edges_total": int(len(g["ii"])), "hw": int(HW),
+                   "keyframes": int(K_graph),
+                   "parallelism": ("single GPU" if world == 1 else
+                                   f"edges sharded by source keyframe over {world} GPUs + RCCL all-reduce of the "
+                                   f"reduced normal equations; rays of the one frame sharded {world} ways")},
+    }
+    if not args.full:
+        _emit(out, rank, world)
+        return
+    out["checks"]["stage2_fallbacks_burst"] = fallbacks_burst
     # ---- sustained figure: >= 400 back-to-back steps (the K-step figure above runs on boost clocks), twice:
     # (a) with the state put back every `reset_every` steps INSIDE the timed region (five device copies, 46 MB) so that
     #     stage 2 keeps solving - the metric's workload, sustained; (b) free-running, where the drifted state makes most
@@ -749,8 +833,6 @@ def main():
     cgraph.replay()
     ev1.record()
     torch.cuda.synchronize()
-    N = graph.ii.shape[0]
-    HW = graph.ht * graph.wd
     alg_bytes = 936.0 * N * HW  # 936 B per edge-pixel
     # the python wrapper adds a coords permute/copy (small); kernel time is reported by rocprof
     # Twenty back-to-back replays of the one launch read the same 89 MB again and again (it stays in the 256 MB Infinity
@@ -995,37 +1077,15 @@ def main():
             corr_traffic = None
     full = world == 1 and N == 36
 
-    out = {
-        "metric": "DSPO BA-update iters/sec + rendered rays/sec, 640x480 Replica keyframe graph",
-        "value": world * args.steps / elapsed,
-        "unit": "BA-update iters/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "soak_steps": soak_steps, "burst_value": world * args.steps / burst_elapsed,
+    out.update({
+        "burst_value": world * args.steps / burst_elapsed,
         "sustained_ms_per_step": sustained_ms, "sustained_steps": sustained_steps,
         "sustained_value": world * 1e3 / sustained_ms,
         "sustained_reset_every": reset_every, "sustained_stage2_fallbacks": fallbacks_sustained,
         "sustained_free_running": {"ms_per_step": sustained_free_ms, "value": world * 1e3 / sustained_free_ms,
                                    "stage2_fallbacks": fallbacks_sustained_free, "stage2_steps": sustained_steps // 2},
-        "checks": {"ba_status": ba_st, "stage2_fallbacks_timed": fallbacks_timed, "stage2_steps": stage2_steps,
-                   "stage2_fallbacks_burst": fallbacks_burst, "state_reset_after_soak": True, "state_finite": True},
         "ba_gn_iters_per_sec": ba_gn_per_s,
         "frontend_config": frontend_cfg,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f16 corr/ConvGRU, f32 Jacobians, f64 solve; render: f32 (decoder matmuls as 3-term f16 splits, f32 accumulate)", "data": "synthetic",
-        "config": {"workload": (f"G8: 8 keyframes, 36 edges, 60x80 (640x480/8), BA itrs=2, DSPO stages alternating, "
-                                 f"context part of the GRU gates (one map per source keyframe) re-evaluated for all keyframes every 12 steps"
-                                if world == 1 else
-                                f"G8 topology over {K_graph} keyframes = {len(g['ii'])} edges (36 per GPU), 60x80, BA itrs=2, "
-                                f"DSPO stages alternating; value = G8-sized (36-edge) updates per second")
-                               + "; multiview_filter.thresh = 0.25 (reference ships 0.01, configs/mono_point_slam.yaml:75: with "
-                                 "untrained weights 0.01 rejects > 80 % of every frame and no depth_scale step would reach stage 2)"
-                               + "; render: 524k-point cloud, one 640x480 view, 10 samples/ray",
-                   "edges_local": int(N), "edges_total": int(len(g["ii"])), "hw": int(HW),
-                   "keyframes": int(K_graph),
-                   "parallelism": ("single GPU" if world == 1 else
-                                   f"edges sharded by source keyframe over {world} GPUs + RCCL all-reduce of the "
-                                   f"reduced normal equations; rays of the one frame sharded {world} ways")},
         "roofline": {"bound": "mfma", "kernel": "conv_pp_kernel<EPI_GRU_ZR> (ConvGRU convz|convr over [net|corr|flow], 320->256, 3x3, + hoisted context term; 256 x 256 ping-pong tile)",
                      "achieved": conv_tf, "peak": MFMA_F16_PEAK_TF, "unit": "TFLOP/s",
                      "frac": conv_tf / MFMA_F16_PEAK_TF, "traffic": conv_traffic if full else None,
@@ -1092,13 +1152,10 @@ def main():
                          "achieved": mlp_tf, "peak": 2500.0 / 3.0, "unit": "TFLOP/s", "frac": mlp_tf / (2500.0 / 3.0),
                          "vs_fp32_mfma_peak": mlp_tf / 157.3,
                          "traffic": None, "flops_per_launch": mlp_flops, "ms_per_launch": mlp_ms},
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_subprocess()
-    if rank == 0:
-        print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
+    _emit(out, rank, world)
 
 
 if __name__ == "__main__":

@@ -3,9 +3,9 @@
 # PMC passes of the correlation lookups and of the decoders, training iteration and low-memory global BA stats, BA solve sizes.
 # Outputs land in gpurun_out/final/; tools/collect_profiles.sh copies them into profiles/ with the round prefix.
 R=$PWD; O=$R/gpurun_out/final; mkdir -p $O
-python bench.py --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err
+python bench.py --steps 20 --warmup 3 --full > $O/bench.json 2> $O/bench.err
 cd /tmp; export TMPDIR=/tmp
-rm -rf /tmp/fb; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fb -o b -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --g8-only > $O/bench_prof.json 2> $O/bench_prof.err
+rm -rf /tmp/fb; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fb -o b -- python $R/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --g8-only > $O/bench_prof.json 2> $O/bench_prof.err
 cp $(find /tmp/fb -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
 python $R/tools/trace_step.py $(find /tmp/fb -name "*kernel_trace.csv" | head -1) corr_dm_encode 20 > $O/step_trace.txt 2>&1
 rm -rf /tmp/fr; rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fr -o r -- python $R/tools/prof_render.py > /dev/null 2>&1
