@@ -109,6 +109,10 @@ SIGNATURES = {
     "glorie_counter_add": (_c_int, [_vp, _c_int, _vp]),
     "glorie_ba_status": (_c_int, [_vp, ctypes.POINTER(_c_int), _vp]),
     "glorie_ba_set_gate": (_c_int, [_vp, _vp, _vp]),
+    "glorie_pix_warp_workspace": (_sz, [_c_int]),
+    "glorie_pix_warp_fwd": (_c_int, [_vp] * 4 + [_c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int] + [_c_f] * 4
+                            + [_vp, _c_int] + [_vp] * 5 + [_vp]),
+    "glorie_pix_warp_bwd": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _vp]),
 }
 
 _lib = None

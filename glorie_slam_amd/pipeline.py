@@ -21,6 +21,7 @@ from .frontend import Frontend
 from .motion_filter import MotionFilter
 from .neural_point import se3_inv
 from .render_train import FeatureAdam
+from .warp_loss import FrameTable, pix_warping_loss
 
 
 def pose_matrix(pose7):
@@ -41,7 +42,8 @@ class SequenceRunner:
     mono_depth_fn(tstamp, image) -> [H,W] depth prior (the reference reads it from the estimator's output directory)."""
 
     def __init__(self, net, video, cfg, npc, decoders, renderer, mono_depth_fn, use_graphs=True, ba_every=4, ba_steps=2,
-                 map_iters=20, map_rays=1000, add_stride=8, seed=43):
+                 map_iters=20, map_rays=1000, add_stride=8, seed=43, pix_warping=None, w_pix_warp_loss=None,
+                 mapping_window_size=None):
         self.net, self.video, self.cfg = net, video, cfg
         self.npc, self.decoders, self.renderer = npc, decoders, renderer
         dev = cfg["device"]
@@ -66,6 +68,15 @@ class SequenceRunner:
         self.map_graph = False
         self.map_graph_stats = {"captures": 0, "replays": 0}
         self.init_state = None                # callable(k, tstamp): the tracker's initial guess for a new keyframe (tests)
+        # the pixel-warping term (mapper.py:326-388, :502-507) over a window of keyframes: cfg["mapping"] keys of the
+        # reference config or the constructor arguments; off by default (window 1, the loss of map_keyframe unchanged)
+        mp = cfg.get("mapping", {})
+        self.pix_warping = bool(mp.get("pix_warping", False) if pix_warping is None else pix_warping)
+        self.w_pix_warp_loss = float(mp.get("w_pix_warp_loss", 1000.0) if w_pix_warp_loss is None else w_pix_warp_loss)
+        self.mapping_window_size = int(mp.get("mapping_window_size", 1) if mapping_window_size is None
+                                       else mapping_window_size)
+        self.warp_losses = []                 # per mapped keyframe with pix_warping: (first, last) value of the warp term
+        self.map_probe = None                 # callable(k, dict of the iteration's tensors), eager iterations only (tests)
 
     # ---- tracker.py:33-77 ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -133,7 +144,8 @@ class SequenceRunner:
 
     def map_keyframe(self, k):
         """seed the keyframe's points, then `map_iters` iterations on `map_rays` of its pixels (depth + colour L1,
-        mapper.py:497-505; learning rates of the colour stage, mapper.py:412-414)"""
+        mapper.py:497-505; learning rates of the colour stage, mapper.py:412-414).  With pix_warping on, the rays are split
+        over a window of keyframes (_warp_window) and the pixel-warping term joins the loss (warp_loss.py)"""
         npc, dec, ren = self.npc, self.decoders, self.renderer
         with torch.no_grad():
             ro, rd, d, col, ii, jj, radius = self._keyframe_rays(k, stride=self.add_stride)
@@ -145,15 +157,27 @@ class SequenceRunner:
         dec.train()
         for p in dec.parameters():
             p.requires_grad_(True)
+        warp = self._warp_window(k) if self.pix_warping else None
         with torch.no_grad():
             view = self._keyframe_view(k)
-            # every iteration's pixel draw in one transfer ([iteration][ii | jj][ray], the generator's order per iteration)
-            draws = torch.stack([torch.stack([torch.randint(0, self.video.wd, (self.map_rays,), generator=self.gen),
-                                              torch.randint(0, self.video.ht, (self.map_rays,), generator=self.gen)])
-                                 for _ in range(self.map_iters)]).to(self.device) if self.map_iters else None
-            # one look at the keyframe's depth map (a host round trip per KEYFRAME): if every pixel carries a depth, no
-            # iteration needs the host - the renderer skips its per-batch zero-depth check and the iteration can be recorded
-            all_depth = bool((view[0] > 0).all())
+            if warp is None:
+                # every iteration's pixel draw in one transfer ([iteration][ii | jj][ray], the generator's order per iteration)
+                draws = torch.stack([torch.stack([torch.randint(0, self.video.wd, (self.map_rays,), generator=self.gen),
+                                                  torch.randint(0, self.video.ht, (self.map_rays,), generator=self.gen)])
+                                     for _ in range(self.map_iters)]).to(self.device) if self.map_iters else None
+                # one look at the keyframe's depth map (a host round trip per KEYFRAME): if every pixel carries a depth, no
+                # iteration needs the host - the renderer skips its per-batch zero-depth check and the iteration can be
+                # recorded
+                all_depth = bool((view[0] > 0).all())
+            else:
+                # map_rays // len(window) pixels of every window frame per iteration (pixs_per_image, mapper.py:584), all
+                # iterations drawn up front: [iteration][ii | jj][frame-major rays]
+                per, n_win = warp["per"], len(warp["window"])
+                draws = torch.stack([torch.stack([torch.cat(c) for c in zip(*[
+                    (torch.randint(0, self.video.wd, (per,), generator=self.gen),
+                     torch.randint(0, self.video.ht, (per,), generator=self.gen)) for _ in range(n_win)])])
+                    for _ in range(self.map_iters)]).to(self.device) if self.map_iters else None
+                all_depth = bool(torch.stack([(warp["views"][f][0] > 0).all() for f in warp["window"]]).all())
         use_graph = bool(getattr(self, "map_graph", True)) and all_depth and self.map_iters >= 4 and \
             str(self.device).startswith("cuda") and getattr(ren, "use_train_path", True)
         opt = FeatureAdam([{"params": list(dec.parameters()), "lr": 0.005}, {"params": [geo], "lr": 0.005},
@@ -163,7 +187,10 @@ class SequenceRunner:
 
         def iteration():
             with torch.no_grad():
-                ro, rd, d, gt_col, _, _, radius = self._keyframe_rays(k, view=view, pix=(pix[0], pix[1]))
+                if warp is None:
+                    ro, rd, d, gt_col, _, _, radius = self._keyframe_rays(k, view=view, pix=(pix[0], pix[1]))
+                else:
+                    ro, rd, d, gt_col, radius = self._window_rays(warp, pix)
             opt.zero_grad()
             depth, _, colour, _, counts = ren.render_batch_ray(npc, dec, rd, ro, self.device, "color", gt_depth=d,
                                                                npc_geo_feats=geo, npc_col_feats=col_f,
@@ -172,7 +199,17 @@ class SequenceRunner:
             # in the forward and one in the backward pass of every iteration)
             seen = ((counts > 0) & (d > 0)).to(depth.dtype)
             loss = (torch.abs(d - depth) * seen).sum() + 0.5 * (torch.abs(gt_col - colour) * seen[:, None]).sum()
+            if warp is not None:
+                # inside the numerator: its weight relative to the L1 sums is the reference's (mapper.py:497-507)
+                w = pix_warping_loss(ro, rd, depth, warp["c2ws"], ren.fx, ren.fy, ren.cx, ren.cy, self.video.wd,
+                                     self.video.ht, warp["frame_ids"], warp["ray_frame"], warp["table"], gt_col,
+                                     nan_to_zero=True)
+                loss = loss + self.w_pix_warp_loss * w
+                warp["value"].copy_(w.detach())
             loss = loss / seen.sum().clamp_min(1)
+            if self.map_probe is not None and not torch.cuda.is_current_stream_capturing():
+                self.map_probe(k, dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(), colour=colour.detach(),
+                                       seen=seen, loss=loss.detach(), warp=warp))
             loss.backward()
             opt.step()
             return loss.detach()
@@ -207,6 +244,8 @@ class SequenceRunner:
                 last = iteration()
                 if first is None:
                     first = last.clone()
+                    if warp is not None:
+                        warp["first"] = warp["value"].clone()
             if graph is not None:
                 # host bookkeeping: the eager iteration and the recording itself each counted one step, the device did
                 # 1 + (map_iters - 1)
@@ -223,7 +262,34 @@ class SequenceRunner:
             npc.update_col_feats(col_f.detach())
         dec.eval()
         self.losses.append((float(first), float(last)))
+        if warp is not None:
+            self.warp_losses.append((float(warp["first"]), float(warp["value"])))
         return self.losses[-1]
+
+    def _warp_window(self, k):
+        """the mapping window of keyframe k with pix_warping on: k and the mapping_window_size - 1 most recent earlier
+        keyframes (the reference picks the earlier ones by overlap with k, mapper.py:176 chosen at :541-549 - that
+        selection is not built here), their views, rays per frame, frame ids and the device table of their images"""
+        window = list(range(max(0, k - self.mapping_window_size + 1), k + 1))
+        with torch.no_grad():
+            views = {f: self._keyframe_view(f) for f in window}
+            per = self.map_rays // len(window)
+            frame_ids = torch.tensor(window, dtype=torch.int64).to(self.device)
+            return {"window": window, "views": views, "per": per, "frame_ids": frame_ids,
+                    "ray_frame": frame_ids.repeat_interleave(per),
+                    "c2ws": torch.stack([views[f][1] for f in window]).float().contiguous(),
+                    "table": FrameTable([self.images[f] for f in window], channels_first=True),
+                    "value": torch.zeros((), device=self.device), "first": None}
+
+    def _window_rays(self, warp, pix):
+        """the rays of one iteration over the window: frame f's slice of `pix` through its own view, depth and image"""
+        per, parts = warp["per"], []
+        for i, f in enumerate(warp["window"]):
+            sl = slice(i * per, (i + 1) * per)
+            parts.append(self._keyframe_rays(f, view=warp["views"][f], pix=(pix[0, sl], pix[1, sl])))
+        ro, rd, d, col = (torch.cat([p[j] for p in parts]) for j in range(4))
+        radius = torch.cat([p[6] for p in parts]) if parts[0][6] is not None else None
+        return ro, rd, d, col, radius
 
     def _capture_iteration(self, iteration):
         """record one mapping iteration into a hipGraph (one memory pool for all keyframes of this runner, kept open by a

@@ -751,6 +751,35 @@ int glorie_adam_multi_dev(const void* table, int n_tensors, long max_numel, cons
                           void* stream);
 int glorie_counter_add(int* counter, int delta, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Pixel-warping loss of the mapping window                                              */
+/* ------------------------------------------------------------------------------------ */
+
+/* Mapper.pix_warping_loss(batch_rays_o, batch_rays_d, depth, c2ws, fx, fy, cx, cy, W, H, frame_indices,
+ * indices_tensor, img_gt_colors, batch_gt_color)
+ *   reference: src/mapper.py:326-388, projection src/utils/common.py:324-350
+ * rays_o, rays_d [N,3] f32, depth [N] f32, ray_frame [N] int64 (indices_tensor), c2ws [M,4,4] f32 (bottom row 0 0 0 1),
+ * frame_indices [M] int64, 0 <= M <= 64.  Images: `images` [M,H,W,3] f32 (the reference layout) when frame_table is
+ * NULL, else frame_table is a DEVICE array of M `const float*`, one image per frame; chw = 1 reads each image as [3,H,W].
+ * gt_color [N,3] f32.  X = o + d * depth is projected into every frame with w2c = inverse(c2w), x negated before K,
+ * zc = z + 1e-5; entry (r, m) is kept when 5 < u < W-5, 5 < v < H-5, zc < 0, frame_indices[m] != ray_frame[r] and ray r
+ * has >= 4 such entries.  Kept entries sample their frame bilinearly at (u - 0.5, v - 0.5) (grid_sample,
+ * align_corners=False, border padding) and add smooth_l1(beta 0.1) against gt_color.
+ * Outputs (device): loss[0] = sum / (3 * kept) (NaN for kept = 0, or 0 with nan_to_zero), scale[0] = 1 / (3 * kept)
+ * (0 for kept = 0), raw_grad [N] = d sum / d depth per ray (0 for a non-finite depth), count[0] = kept (may be NULL).
+ * workspace: glorie_pix_warp_workspace(N) bytes.  Two launches, fixed-order reductions (bitwise repeatable), no host
+ * synchronisation. */
+size_t glorie_pix_warp_workspace(int N);
+int glorie_pix_warp_fwd(const float* rays_o, const float* rays_d, const float* depth, const int64_t* ray_frame, int N,
+                        const float* c2ws, const int64_t* frame_indices, int M, const float* images,
+                        const void* frame_table, int chw, int H, int W, float fx, float fy, float cx, float cy,
+                        const float* gt_color, int nan_to_zero, void* workspace, float* loss, float* raw_grad,
+                        float* scale, int* count, void* stream);
+/* backward of glorie_pix_warp_fwd with respect to depth: grad_depth [N] = raw_grad * grad_out[0] * scale[0]
+ * (grad_out: the loss's incoming gradient, one float on the device).  One launch. */
+int glorie_pix_warp_bwd(const float* raw_grad, const float* scale, const float* grad_out, int N, float* grad_depth,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
