@@ -113,6 +113,10 @@ SIGNATURES = {
     "glorie_pix_warp_fwd": (_c_int, [_vp] * 4 + [_c_int, _vp, _vp, _c_int, _vp, _vp, _c_int, _c_int, _c_int] + [_c_f] * 4
                             + [_vp, _c_int] + [_vp] * 5 + [_vp]),
     "glorie_pix_warp_bwd": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _vp]),
+    "glorie_frustum_select_workspace": (_sz, [_c_int]),
+    "glorie_frustum_select": (_c_int, [_vp, _c_int, _vp] + [_c_f] * 4 + [_c_int, _c_int, _c_f] + [_vp] * 6),
+    "glorie_keyframe_overlap": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _c_int] + [_c_f] * 4
+                                + [_c_int, _c_int, _c_f, _vp, _vp]),
 }
 
 _lib = None

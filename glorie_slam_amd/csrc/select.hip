@@ -1,0 +1,269 @@
+// Keyframe selection of the mapper: frustum feature selection and the keyframe overlap count
+// (reference: src/mapper.py:126-174 Mapper.get_mask_from_c2w, :176-244 Mapper.keyframe_selection_overlap).
+//
+// Both take camera-to-world matrices in the renderer's OpenGL convention (what the reference passes after
+// `c2w[:3, 1:3] *= -1`) and invert the rigid transform in the kernel: w2c = [R^T | -R^T t].  A point projects as in the
+// reference: camera coordinates w2c . p, x negated, uv = K . cam, z = uv_z + 1e-5, uv = uv_xy / z.
+//
+// Frustum selection, four launches and one memset, no host synchronisation (the count stays on the device):
+//   frustum_sample_kernel   one thread per point: project, sample the depth map bilinearly at (u, v) as
+//                           cv2.remap(INTER_LINEAR, BORDER_CONSTANT 0) does - coordinates rounded to 1/32 px, weights
+//                           and sum in fp32 (cv2 sums in its own order: the last bit may differ) - store (-z or -inf
+//                           outside the edge band, sampled depth), and fold the sampled depth into a global maximum
+//                           (an integer atomic max on an order-preserving key of the float: exact in any order)
+//   frustum_mask_kernel     sampled depth 0 -> that maximum (`depths[zero_mask] = np.max(depths)`), keep when
+//                           0 <= -z <= depth + 0.5; one kept count per workgroup (wave ballots, no atomics)
+//   select_scan_kernel      one workgroup: exclusive scan of the workgroup counts -> offsets and the total count
+//   frustum_indices_kernel  (only when indices are asked for) the kept points' indices in ascending order
+// Overlap count, one launch: overlap_count_kernel, one workgroup per keyframe, an integer sum over the ray samples.
+// Every result is an integer decision or count: repeated calls are bitwise equal.
+#include "common.hiph"
+
+using namespace glorie;
+
+namespace {
+
+constexpr int kSelThreads = 256;          // 4 waves of 64
+constexpr int kSelWaves = kSelThreads / 64;
+constexpr int kScanThreads = 1024;
+
+struct Rigid {
+  float r[12];                            // w2c, row-major 3x4
+};
+
+// w2c of a rigid c2w [4,4] row-major: R^T and -R^T t
+__device__ __forceinline__ Rigid rigid_inverse(const float* __restrict__ c2w) {
+  Rigid w;
+#pragma unroll
+  for (int row = 0; row < 3; ++row) {
+    const float a = c2w[0 + row], b = c2w[4 + row], c = c2w[8 + row];     // column `row` of R
+    w.r[row * 4 + 0] = a;
+    w.r[row * 4 + 1] = b;
+    w.r[row * 4 + 2] = c;
+    w.r[row * 4 + 3] = -(a * c2w[3] + b * c2w[7] + c * c2w[11]);
+  }
+  return w;
+}
+
+struct Proj {
+  float u, v, z;                          // z carries the + 1e-5
+};
+
+__device__ __forceinline__ Proj project(const float* w, float X, float Y, float Z, float fx, float fy, float cx,
+                                        float cy) {
+  const float a = w[0] * X + w[1] * Y + w[2] * Z + w[3];
+  const float b = w[4] * X + w[5] * Y + w[6] * Z + w[7];
+  const float c = w[8] * X + w[9] * Y + w[10] * Z + w[11];
+  Proj p;
+  p.z = c + 1e-5f;
+  p.u = (fx * (-a) + cx * c) / p.z;
+  p.v = (fy * b + cy * c) / p.z;
+  return p;
+}
+
+__device__ __forceinline__ float depth_texel(const float* __restrict__ depth, int H, int W, int x, int y) {
+  return (x < 0 || y < 0 || x >= W || y >= H) ? 0.f : depth[(size_t)y * W + x];
+}
+
+// cv2.remap(depth, u, v, INTER_LINEAR) with BORDER_CONSTANT 0 at one point: the map coordinate is rounded to a
+// multiple of 1/32 px (INTER_BITS = 5, round to nearest even), neighbours outside the image read 0, a non-finite or far
+// out coordinate samples 0
+__device__ __forceinline__ float remap_linear(const float* __restrict__ depth, int H, int W, float u, float v) {
+  if (!(u > -2.f && u < (float)W + 1.f && v > -2.f && v < (float)H + 1.f)) return 0.f;
+  const int X = __float2int_rn(u * 32.f), Y = __float2int_rn(v * 32.f);
+  const int x0 = X >> 5, y0 = Y >> 5;
+  const float ax = (float)(X & 31) * (1.f / 32.f), ay = (float)(Y & 31) * (1.f / 32.f);
+  const float w00 = (1.f - ay) * (1.f - ax), w01 = (1.f - ay) * ax, w10 = ay * (1.f - ax), w11 = ay * ax;
+  return depth_texel(depth, H, W, x0, y0) * w00 + depth_texel(depth, H, W, x0 + 1, y0) * w01 +
+         depth_texel(depth, H, W, x0, y0 + 1) * w10 + depth_texel(depth, H, W, x0 + 1, y0 + 1) * w11;
+}
+
+// order-preserving unsigned key of a float (larger float -> larger key; 0 is below every key of a non-NaN float)
+__device__ __forceinline__ unsigned int float_key(float f) {
+  const unsigned int b = __float_as_uint(f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__device__ __forceinline__ float key_float(unsigned int k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__global__ void __launch_bounds__(kSelThreads)
+frustum_sample_kernel(const float* __restrict__ points, int n, const float* __restrict__ c2w, float fx, float fy,
+                      float cx, float cy, int H, int W, float edge, const float* __restrict__ depth,
+                      float2* __restrict__ zd, unsigned int* __restrict__ max_key) {
+  __shared__ unsigned int red[kSelWaves];
+  const Rigid w = rigid_inverse(c2w);
+  const int i = blockIdx.x * kSelThreads + threadIdx.x;
+  unsigned int key = 0;
+  if (i < n) {
+    const Proj p = project(w.r, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], fx, fy,
+                           cx, cy);
+    const float s = remap_linear(depth, H, W, p.u, p.v);
+    const bool in = p.u < (float)W - edge && p.u > edge && p.v < (float)H - edge && p.v > edge;
+    zd[i] = make_float2(in ? -p.z : -INFINITY, s);
+    key = float_key(s);
+  }
+  // workgroup maximum, then one atomic per workgroup
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) key = max(key, (unsigned int)__shfl_xor((int)key, off, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned int m = red[0];
+    for (int k = 1; k < kSelWaves; ++k) m = max(m, red[k]);
+    atomicMax(max_key, m);
+  }
+}
+
+__global__ void __launch_bounds__(kSelThreads)
+frustum_mask_kernel(const float2* __restrict__ zd, int n, const unsigned int* __restrict__ max_key,
+                    unsigned char* __restrict__ mask, int* __restrict__ block_count) {
+  __shared__ int red[kSelWaves];
+  const float dmax = key_float(*max_key);
+  const int i = blockIdx.x * kSelThreads + threadIdx.x;
+  bool keep = false;
+  if (i < n) {
+    const float2 e = zd[i];
+    const float d = e.y == 0.f ? dmax : e.y;
+    keep = 0.f <= e.x && e.x <= d + 0.5f;
+    mask[i] = keep ? 1 : 0;
+  }
+  const unsigned long long b = __ballot(keep);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = __popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0;
+    for (int k = 0; k < kSelWaves; ++k) c += red[k];
+    block_count[blockIdx.x] = c;
+  }
+}
+
+// one workgroup: offsets[b] = sum of counts[0, b), total[0] = sum of all
+__global__ void __launch_bounds__(kScanThreads)
+select_scan_kernel(const int* __restrict__ counts, int n_blocks, int* __restrict__ offsets, int* __restrict__ total) {
+  __shared__ int buf[kScanThreads];
+  __shared__ int carry;
+  const int tid = threadIdx.x;
+  if (tid == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < n_blocks; base += kScanThreads) {
+    const int v = base + tid < n_blocks ? counts[base + tid] : 0;
+    buf[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < kScanThreads; off <<= 1) {          // inclusive Hillis-Steele scan
+      const int add = tid >= off ? buf[tid - off] : 0;
+      __syncthreads();
+      buf[tid] += add;
+      __syncthreads();
+    }
+    if (base + tid < n_blocks) offsets[base + tid] = carry + buf[tid] - v;
+    __syncthreads();
+    if (tid == 0) carry += buf[kScanThreads - 1];
+    __syncthreads();
+  }
+  if (tid == 0) total[0] = carry;
+}
+
+__global__ void __launch_bounds__(kSelThreads)
+frustum_indices_kernel(const unsigned char* __restrict__ mask, int n, const int* __restrict__ offsets,
+                       int64_t* __restrict__ indices) {
+  __shared__ int wave_base[kSelWaves];
+  const int i = blockIdx.x * kSelThreads + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool keep = i < n && mask[i] != 0;
+  const unsigned long long b = __ballot(keep);
+  if (lane == 0) wave_base[wave] = __popcll(b);
+  __syncthreads();
+  int base = offsets[blockIdx.x];
+  for (int k = 0; k < wave; ++k) base += wave_base[k];
+  if (keep) indices[base + __popcll(b & ((1ull << lane) - 1ull))] = i;
+}
+
+// one workgroup per keyframe: samples z = near (1 - t) + far t of every ray with depth > 0 (near = 0.8 d, far = d + 0.5,
+// t = linspace(0, 1, n_samples)), counted when edge < u < W - edge, edge < v < H - edge and z < 0
+__global__ void __launch_bounds__(kSelThreads)
+overlap_count_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                     const float* __restrict__ depth, int R, int n_samples, const float* __restrict__ c2ws, float fx,
+                     float fy, float cx, float cy, int H, int W, float edge, int* __restrict__ inside) {
+  __shared__ int red[kSelWaves];
+  const Rigid w = rigid_inverse(c2ws + 16 * (size_t)blockIdx.x);
+  const int total = R * n_samples;
+  const float step = n_samples > 1 ? 1.f / (float)(n_samples - 1) : 0.f;
+  int count = 0;
+  for (int e = threadIdx.x; e < total; e += kSelThreads) {
+    const int r = e / n_samples, s = e - r * n_samples;
+    const float d = depth[r];
+    if (!(d > 0.f)) continue;                                   // get_samples(..., depth_filter=True)
+    // torch.linspace(0, 1, S): the first half from the start, the second half from the end
+    const float t = s < n_samples / 2 ? (float)s * step : 1.f - (float)(n_samples - 1 - s) * step;
+    const float zs = (0.8f * d) * (1.f - t) + (d + 0.5f) * t;
+    const Proj p = project(w.r, rays_o[3 * r] + rays_d[3 * r] * zs, rays_o[3 * r + 1] + rays_d[3 * r + 1] * zs,
+                           rays_o[3 * r + 2] + rays_d[3 * r + 2] * zs, fx, fy, cx, cy);
+    count += (p.u < (float)W - edge && p.u > edge && p.v < (float)H - edge && p.v > edge && p.z < 0.f) ? 1 : 0;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = count;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0;
+    for (int k = 0; k < kSelWaves; ++k) c += red[k];
+    inside[blockIdx.x] = c;
+  }
+}
+
+inline int sel_blocks(int n) { return (n + kSelThreads - 1) / kSelThreads; }
+
+// workspace layout: zd float2 [n] | block counts int [B] | offsets int [B] | max key uint (8-byte aligned pieces)
+inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
+
+}  // namespace
+
+extern "C" size_t glorie_frustum_select_workspace(int n) {
+  if (n < 0) return 0;
+  const size_t B = (size_t)sel_blocks(n);
+  return align8((size_t)n * sizeof(float2)) + 2 * align8(B * sizeof(int)) + 8;
+}
+
+extern "C" int glorie_frustum_select(const float* points, int n, const float* c2w, float fx, float fy, float cx,
+                                     float cy, int H, int W, float edge, const float* depth, void* workspace,
+                                     unsigned char* mask, int* count, int64_t* indices, void* stream) {
+  if (n < 0 || H <= 0 || W <= 0 || !count) return GLORIE_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (n == 0) return check_hip(hipMemsetAsync(count, 0, sizeof(int), st));
+  if (!points || !c2w || !depth || !workspace || !mask) return GLORIE_EINVAL;
+  const int B = sel_blocks(n);
+  char* ws = reinterpret_cast<char*>(workspace);
+  float2* zd = reinterpret_cast<float2*>(ws);
+  int* block_count = reinterpret_cast<int*>(ws + align8((size_t)n * sizeof(float2)));
+  int* offsets = reinterpret_cast<int*>(reinterpret_cast<char*>(block_count) + align8((size_t)B * sizeof(int)));
+  unsigned int* max_key = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(offsets) +
+                                                          align8((size_t)B * sizeof(int)));
+  GLORIE_TRY(check_hip(hipMemsetAsync(max_key, 0, sizeof(unsigned int), st)));
+  hipLaunchKernelGGL(frustum_sample_kernel, dim3(B), dim3(kSelThreads), 0, st, points, n, c2w, fx, fy, cx, cy, H, W,
+                     edge, depth, zd, max_key);
+  GLORIE_TRY(check_launch());
+  hipLaunchKernelGGL(frustum_mask_kernel, dim3(B), dim3(kSelThreads), 0, st, zd, n, max_key, mask, block_count);
+  GLORIE_TRY(check_launch());
+  hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, block_count, B, offsets, count);
+  GLORIE_TRY(check_launch());
+  if (indices) {
+    hipLaunchKernelGGL(frustum_indices_kernel, dim3(B), dim3(kSelThreads), 0, st, mask, n, offsets, indices);
+    GLORIE_TRY(check_launch());
+  }
+  return GLORIE_OK;
+}
+
+extern "C" int glorie_keyframe_overlap(const float* rays_o, const float* rays_d, const float* depth, int R,
+                                       int n_samples, const float* c2ws, int K, float fx, float fy, float cx, float cy,
+                                       int H, int W, float edge, int* inside, void* stream) {
+  if (R < 0 || K < 0 || n_samples < 1 || H <= 0 || W <= 0) return GLORIE_EINVAL;
+  if ((long long)R * n_samples > 0x7fffffffLL) return GLORIE_EINVAL;
+  if (K == 0) return GLORIE_OK;
+  if (!c2ws || !inside) return GLORIE_EINVAL;
+  if (R > 0 && (!rays_o || !rays_d || !depth)) return GLORIE_EINVAL;
+  hipLaunchKernelGGL(overlap_count_kernel, dim3(K), dim3(kSelThreads), 0, (hipStream_t)stream, rays_o, rays_d, depth,
+                     R, n_samples, c2ws, fx, fy, cx, cy, H, W, edge, inside);
+  return check_launch();
+}

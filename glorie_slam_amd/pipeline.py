@@ -18,6 +18,7 @@ import torch
 from .backend import Backend
 from .common import get_rays_from_uv
 from .frontend import Frontend
+from .keyframe_select import frustum_feature_mask, keyframe_selection_overlap, random_select
 from .motion_filter import MotionFilter
 from .neural_point import se3_inv
 from .render_train import FeatureAdam
@@ -43,7 +44,8 @@ class SequenceRunner:
 
     def __init__(self, net, video, cfg, npc, decoders, renderer, mono_depth_fn, use_graphs=True, ba_every=4, ba_steps=2,
                  map_iters=20, map_rays=1000, add_stride=8, seed=43, pix_warping=None, w_pix_warp_loss=None,
-                 mapping_window_size=None):
+                 mapping_window_size=None, keyframe_selection_method=None, frustum_feature_selection=None,
+                 frustum_edge=None):
         self.net, self.video, self.cfg = net, video, cfg
         self.npc, self.decoders, self.renderer = npc, decoders, renderer
         dev = cfg["device"]
@@ -76,6 +78,19 @@ class SequenceRunner:
         self.mapping_window_size = int(mp.get("mapping_window_size", 1) if mapping_window_size is None
                                        else mapping_window_size)
         self.warp_losses = []                 # per mapped keyframe with pix_warping: (first, last) value of the warp term
+        # keyframe selection (mapper.py:541-554) and frustum feature selection (:591-595, :675-677): cfg["mapping"] keys
+        # or the constructor arguments (keyframe_selection_method=False: off whatever the config says).  Without a
+        # method the window is k alone, or k and the most recent keyframes with pix_warping; with one it is the selected
+        # keyframes of [0, k-1), then k-1, then k
+        method = mp.get("keyframe_selection_method") if keyframe_selection_method is None else keyframe_selection_method
+        if method not in (None, False, "", "overlap", "global"):
+            raise ValueError(f"keyframe_selection_method must be 'overlap' or 'global', got {method!r}")
+        self.keyframe_selection_method = method or None
+        self.frustum_feature_selection = bool(mp.get("frustum_feature_selection", False)
+                                              if frustum_feature_selection is None else frustum_feature_selection)
+        self.frustum_edge = float(mp.get("frustum_edge", -4) if frustum_edge is None else frustum_edge)
+        self.windows = []                     # per mapped keyframe: its mapping window (keyframe ids, k last)
+        self.frustum_counts = []              # per mapped keyframe with frustum selection: the number of trained points
         self.map_probe = None                 # callable(k, dict of the iteration's tensors), eager iterations only (tests)
 
     # ---- tracker.py:33-77 ------------------------------------------------------------------------------------------
@@ -144,8 +159,10 @@ class SequenceRunner:
 
     def map_keyframe(self, k):
         """seed the keyframe's points, then `map_iters` iterations on `map_rays` of its pixels (depth + colour L1,
-        mapper.py:497-505; learning rates of the colour stage, mapper.py:412-414).  With pix_warping on, the rays are split
-        over a window of keyframes (_warp_window) and the pixel-warping term joins the loss (warp_loss.py)"""
+        mapper.py:497-505; learning rates of the colour stage, mapper.py:412-414).  With pix_warping on or a
+        keyframe_selection_method, the rays are split over a window of keyframes (_map_window); with pix_warping the
+        pixel-warping term joins the loss (warp_loss.py).  With frustum_feature_selection only the feature rows inside
+        the keyframe's frustum are trained (keyframe_select.py; FeatureAdam's row masks)"""
         npc, dec, ren = self.npc, self.decoders, self.renderer
         with torch.no_grad():
             ro, rd, d, col, ii, jj, radius = self._keyframe_rays(k, stride=self.add_stride)
@@ -157,10 +174,18 @@ class SequenceRunner:
         dec.train()
         for p in dec.parameters():
             p.requires_grad_(True)
-        warp = self._warp_window(k) if self.pix_warping else None
         with torch.no_grad():
             view = self._keyframe_view(k)
-            if warp is None:
+            win = self._map_window(k, view) if (self.pix_warping or self.keyframe_selection_method) else None
+            warp = win if self.pix_warping else None
+            self.windows.append(win["window"] if win is not None else [k])
+            # the rows the iterations may change: inside the frustum of this view, against the depth the iteration reads
+            # (get_mask_from_c2w, mapper.py:591-595); the count stays on the device until the keyframe is done
+            frustum = frustum_feature_mask(npc.cloud_pos(), view[1], view[0], ren.fx, ren.fy, ren.cx, ren.cy,
+                                           self.video.ht, self.video.wd, self.frustum_edge) \
+                if self.frustum_feature_selection else None
+            row_masks = {id(geo): frustum[0], id(col_f): frustum[0]} if frustum is not None else None
+            if win is None:
                 # every iteration's pixel draw in one transfer ([iteration][ii | jj][ray], the generator's order per iteration)
                 draws = torch.stack([torch.stack([torch.randint(0, self.video.wd, (self.map_rays,), generator=self.gen),
                                                   torch.randint(0, self.video.ht, (self.map_rays,), generator=self.gen)])
@@ -172,12 +197,12 @@ class SequenceRunner:
             else:
                 # map_rays // len(window) pixels of every window frame per iteration (pixs_per_image, mapper.py:584), all
                 # iterations drawn up front: [iteration][ii | jj][frame-major rays]
-                per, n_win = warp["per"], len(warp["window"])
+                per, n_win = win["per"], len(win["window"])
                 draws = torch.stack([torch.stack([torch.cat(c) for c in zip(*[
                     (torch.randint(0, self.video.wd, (per,), generator=self.gen),
                      torch.randint(0, self.video.ht, (per,), generator=self.gen)) for _ in range(n_win)])])
                     for _ in range(self.map_iters)]).to(self.device) if self.map_iters else None
-                all_depth = bool(torch.stack([(warp["views"][f][0] > 0).all() for f in warp["window"]]).all())
+                all_depth = bool(torch.stack([(win["views"][f][0] > 0).all() for f in win["window"]]).all())
         use_graph = bool(getattr(self, "map_graph", True)) and all_depth and self.map_iters >= 4 and \
             str(self.device).startswith("cuda") and getattr(ren, "use_train_path", True)
         opt = FeatureAdam([{"params": list(dec.parameters()), "lr": 0.005}, {"params": [geo], "lr": 0.005},
@@ -187,10 +212,10 @@ class SequenceRunner:
 
         def iteration():
             with torch.no_grad():
-                if warp is None:
+                if win is None:
                     ro, rd, d, gt_col, _, _, radius = self._keyframe_rays(k, view=view, pix=(pix[0], pix[1]))
                 else:
-                    ro, rd, d, gt_col, radius = self._window_rays(warp, pix)
+                    ro, rd, d, gt_col, radius = self._window_rays(win, pix)
             opt.zero_grad()
             depth, _, colour, _, counts = ren.render_batch_ray(npc, dec, rd, ro, self.device, "color", gt_depth=d,
                                                                npc_geo_feats=geo, npc_col_feats=col_f,
@@ -209,9 +234,10 @@ class SequenceRunner:
             loss = loss / seen.sum().clamp_min(1)
             if self.map_probe is not None and not torch.cuda.is_current_stream_capturing():
                 self.map_probe(k, dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(), colour=colour.detach(),
-                                       seen=seen, loss=loss.detach(), warp=warp))
+                                       seen=seen, loss=loss.detach(), warp=warp, window=win,
+                                       frustum=frustum[0] if frustum is not None else None))
             loss.backward()
-            opt.step()
+            opt.step(row_masks=row_masks)
             return loss.detach()
 
         first = last = None
@@ -264,29 +290,49 @@ class SequenceRunner:
         self.losses.append((float(first), float(last)))
         if warp is not None:
             self.warp_losses.append((float(warp["first"]), float(warp["value"])))
+        if frustum is not None:
+            self.frustum_counts.append(int(frustum[1]))
         return self.losses[-1]
 
-    def _warp_window(self, k):
-        """the mapping window of keyframe k with pix_warping on: k and the mapping_window_size - 1 most recent earlier
-        keyframes (the reference picks the earlier ones by overlap with k, mapper.py:176 chosen at :541-549 - that
-        selection is not built here), their views, rays per frame, frame ids and the device table of their images"""
-        window = list(range(max(0, k - self.mapping_window_size + 1), k + 1))
+    def _select_keyframes(self, k, view):
+        """the keyframes of [0, k-1) that join k-1 and k in the window of keyframe k: up to mapping_window_size - 2 of
+        them (mapper.py:541-549: the candidates are keyframe_dict[:-1]), by overlap with k's view or at random"""
+        num, n_cand = max(self.mapping_window_size - 2, 0), max(k - 1, 0)
+        if num == 0 or n_cand == 0:
+            return []
+        if self.keyframe_selection_method == "global":
+            return random_select(n_cand, num, generator=self.gen)
+        ren = self.renderer
+        c2ws = torch.stack([self._keyframe_view(f)[1] for f in range(n_cand)])
+        return keyframe_selection_overlap(self.images.get(k), view[0], view[1], c2ws, num, ren.fx, ren.fy, ren.cx, ren.cy,
+                                          generator=self.gen)
+
+    def _map_window(self, k, view):
+        """the mapping window of keyframe k (k last) with its views, rays per frame and frame ids; with pix_warping also
+        the window's c2ws and the device table of its images.  Without a keyframe_selection_method: k and the
+        mapping_window_size - 1 most recent earlier keyframes; with one: the selected keyframes, k-1, k"""
+        if self.keyframe_selection_method:
+            window = self._select_keyframes(k, view) + ([k - 1] if k > 0 else []) + [k]
+        else:
+            window = list(range(max(0, k - self.mapping_window_size + 1), k + 1))
         with torch.no_grad():
-            views = {f: self._keyframe_view(f) for f in window}
+            views = {f: (view if f == k else self._keyframe_view(f)) for f in window}
             per = self.map_rays // len(window)
             frame_ids = torch.tensor(window, dtype=torch.int64).to(self.device)
-            return {"window": window, "views": views, "per": per, "frame_ids": frame_ids,
-                    "ray_frame": frame_ids.repeat_interleave(per),
-                    "c2ws": torch.stack([views[f][1] for f in window]).float().contiguous(),
-                    "table": FrameTable([self.images[f] for f in window], channels_first=True),
-                    "value": torch.zeros((), device=self.device), "first": None}
+            win = {"window": window, "views": views, "per": per, "frame_ids": frame_ids,
+                   "ray_frame": frame_ids.repeat_interleave(per)}
+            if self.pix_warping:
+                win.update({"c2ws": torch.stack([views[f][1] for f in window]).float().contiguous(),
+                            "table": FrameTable([self.images[f] for f in window], channels_first=True),
+                            "value": torch.zeros((), device=self.device), "first": None})
+            return win
 
-    def _window_rays(self, warp, pix):
+    def _window_rays(self, win, pix):
         """the rays of one iteration over the window: frame f's slice of `pix` through its own view, depth and image"""
-        per, parts = warp["per"], []
-        for i, f in enumerate(warp["window"]):
+        per, parts = win["per"], []
+        for i, f in enumerate(win["window"]):
             sl = slice(i * per, (i + 1) * per)
-            parts.append(self._keyframe_rays(f, view=warp["views"][f], pix=(pix[0, sl], pix[1, sl])))
+            parts.append(self._keyframe_rays(f, view=win["views"][f], pix=(pix[0, sl], pix[1, sl])))
         ro, rd, d, col = (torch.cat([p[j] for p in parts]) for j in range(4))
         radius = torch.cat([p[6] for p in parts]) if parts[0][6] is not None else None
         return ro, rd, d, col, radius

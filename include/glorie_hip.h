@@ -780,6 +780,35 @@ int glorie_pix_warp_fwd(const float* rays_o, const float* rays_d, const float* d
 int glorie_pix_warp_bwd(const float* raw_grad, const float* scale, const float* grad_out, int N, float* grad_depth,
                         void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Keyframe selection of the mapper                                                      */
+/* ------------------------------------------------------------------------------------ */
+
+/* Mapper.get_mask_from_c2w(c2w, depth_np)   reference: src/mapper.py:126-174
+ * points [n,3] f32, c2w [4,4] f32 in the renderer's OpenGL convention (rigid: inverted as R^T, -R^T t in the kernel),
+ * depth [H,W] f32.  A point projects with x negated, uv = K cam, z = uv_z + 1e-5, uv = uv_xy / z; its depth sample is
+ * bilinear at (u, v) as cv2.remap(INTER_LINEAR, BORDER_CONSTANT 0): coordinates rounded to 1/32 px, neighbours outside
+ * the image read 0, weights and sum in fp32 (the last bit of a sample may differ from cv2's), a non-finite uv samples 0.
+ * A sample of 0 is replaced by the maximum sample over all n points.  Kept: edge < u < W-edge, edge < v < H-edge (edge may
+ * be negative) and 0 <= -z <= sample + 0.5.
+ * Outputs (device): mask [n] uint8, count[0] int32 = number kept, and, when indices is not NULL, indices [n] int64 whose
+ * first count entries are the kept points in ascending order (the rest untouched).  n = 0 writes count 0 only.
+ * workspace: glorie_frustum_select_workspace(n) bytes.  A memset and three or four launches, integer reductions only
+ * (bitwise repeatable), no host synchronisation. */
+size_t glorie_frustum_select_workspace(int n);
+int glorie_frustum_select(const float* points, int n, const float* c2w, float fx, float fy, float cx, float cy, int H,
+                          int W, float edge, const float* depth, void* workspace, unsigned char* mask, int* count,
+                          int64_t* indices, void* stream);
+/* the overlap figure of Mapper.keyframe_selection_overlap   reference: src/mapper.py:176-244
+ * rays_o, rays_d [R,3] f32, depth [R] f32 of the current view (rays whose depth is not > 0 are skipped, get_samples'
+ * depth_filter); n_samples points per ray at z = near (1-t) + far t, near = 0.8 d, far = d + 0.5, t = linspace(0, 1,
+ * n_samples).  c2ws [K,4,4] f32, OpenGL convention, rigid.  inside [K] int32 = number of samples with
+ * edge < u < W-edge, edge < v < H-edge and z < 0 in keyframe k (the reference's edge is 20).  One launch, one workgroup per
+ * keyframe, integer sums; K = 0 launches nothing, R = 0 writes zeros. */
+int glorie_keyframe_overlap(const float* rays_o, const float* rays_d, const float* depth, int R, int n_samples,
+                            const float* c2ws, int K, float fx, float fy, float cx, float cy, int H, int W, float edge,
+                            int* inside, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
