@@ -117,6 +117,9 @@ SIGNATURES = {
     "glorie_frustum_select": (_c_int, [_vp, _c_int, _vp] + [_c_f] * 4 + [_c_int, _c_int, _c_f] + [_vp] * 6),
     "glorie_keyframe_overlap": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _c_int] + [_c_f] * 4
                                 + [_c_int, _c_int, _c_f, _vp, _vp]),
+    "glorie_color_grad_maps": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp] + [ctypes.c_double] * 4 + [_vp] * 6),
+    "glorie_topm_workspace": (_sz, [_c_int]),
+    "glorie_topm": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -16,6 +16,8 @@ import time
 import torch
 
 from .backend import Backend
+from .color_grad import (COLOR_GRAD_THRESHOLD, RADIUS_ADD_MAX, RADIUS_ADD_MIN, RADIUS_QUERY_RATIO, color_grad_maps,
+                         get_samples_with_pixel_grad)
 from .common import get_rays_from_uv
 from .frontend import Frontend
 from .keyframe_select import frustum_feature_mask, keyframe_selection_overlap, random_select
@@ -45,7 +47,7 @@ class SequenceRunner:
     def __init__(self, net, video, cfg, npc, decoders, renderer, mono_depth_fn, use_graphs=True, ba_every=4, ba_steps=2,
                  map_iters=20, map_rays=1000, add_stride=8, seed=43, pix_warping=None, w_pix_warp_loss=None,
                  mapping_window_size=None, keyframe_selection_method=None, frustum_feature_selection=None,
-                 frustum_edge=None):
+                 frustum_edge=None, color_grad_radius=None, pixels_based_on_color_grad=None):
         self.net, self.video, self.cfg = net, video, cfg
         self.npc, self.decoders, self.renderer = npc, decoders, renderer
         dev = cfg["device"]
@@ -92,6 +94,24 @@ class SequenceRunner:
         self.windows = []                     # per mapped keyframe: its mapping window (keyframe ids, k last)
         self.frustum_counts = []              # per mapped keyframe with frustum selection: the number of trained points
         self.map_probe = None                 # callable(k, dict of the iteration's tensors), eager iterations only (tests)
+        # colour-gradient search radii (mapper.py:767-784): on when the cloud uses dynamic radii and cfg["pointcloud"] has
+        # the four keys, or by the constructor argument (True without the keys: the master config's values).  Insertion
+        # rays then take dynamic_r_add / 3 * depth of their pixel, training rays their frame's dynamic_r_query / 3 * depth;
+        # off, every ray keeps the constant 0.5 * (radius_add + radius_query)
+        pc = cfg.get("pointcloud", {})
+        keys = ("radius_add_max", "radius_add_min", "radius_query_ratio", "color_grad_threshold")
+        on = (bool(getattr(npc, "use_dynamic_radius", False)) and all(k in pc for k in keys)) \
+            if color_grad_radius is None else bool(color_grad_radius)
+        if on and not getattr(npc, "use_dynamic_radius", False):
+            raise ValueError("color_grad_radius needs a point cloud with use_dynamic_radius")
+        self.color_grad = dict(color_grad_threshold=float(pc.get("color_grad_threshold", COLOR_GRAD_THRESHOLD)),
+                               radius_add_max=float(pc.get("radius_add_max", RADIUS_ADD_MAX)),
+                               radius_add_min=float(pc.get("radius_add_min", RADIUS_ADD_MIN)),
+                               radius_query_ratio=float(pc.get("radius_query_ratio", RADIUS_QUERY_RATIO))) if on else None
+        # the second anchoring pass on the pixels of highest colour gradient (mapper.py:312-322): cfg["mapping"] key or
+        # the constructor argument; 0 is off
+        self.pixels_based_on_color_grad = int(mp.get("pixels_based_on_color_grad", 0)
+                                              if pixels_based_on_color_grad is None else pixels_based_on_color_grad)
 
     # ---- tracker.py:33-77 ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -131,11 +151,12 @@ class SequenceRunner:
         c2w[:3, 2] *= -1
         return depth, c2w
 
-    def _keyframe_rays(self, k, stride=1, count=None, view=None, pix=None):
+    def _keyframe_rays(self, k, stride=1, count=None, view=None, pix=None, radius_map=None):
         """pixels of keyframe k with a valid depth -> rays, depth, colour, pixel ids (common.py:39-54 ray convention).
         view: `_keyframe_view(k)` computed by the caller; pix: the (ii, jj) pixel draw of this call, already on the device
         (the mapping loop draws all its iterations at once: a per-iteration host-to-device copy from pageable memory blocks
-        the host until the stream has drained)"""
+        the host until the stream has drained); radius_map: a per-pixel [H,W] radius of keyframe k (_radius_maps) the rays
+        gather from, else the constant one"""
         v = self.video
         H, W = v.ht, v.wd
         cam = self.renderer
@@ -153,7 +174,9 @@ class SequenceRunner:
         d = depth[jj, ii]
         col = self.images[k][:, jj, ii].t().contiguous()
         radius = None
-        if self.npc.use_dynamic_radius:
+        if radius_map is not None:
+            radius = radius_map[jj, ii]
+        elif self.npc.use_dynamic_radius:
             radius = torch.full_like(d, 0.5 * (self.npc.radius_add + self.npc.radius_query))
         return ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous(), d, col, ii, jj, radius
 
@@ -165,8 +188,13 @@ class SequenceRunner:
         the keyframe's frustum are trained (keyframe_select.py; FeatureAdam's row masks)"""
         npc, dec, ren = self.npc, self.decoders, self.renderer
         with torch.no_grad():
-            ro, rd, d, col, ii, jj, radius = self._keyframe_rays(k, stride=self.add_stride)
+            # colour-gradient radii of k scaled by its depth: (r_add, r_query) [H,W], or None
+            rmaps = self._radius_maps(k, self._keyframe_view(k)) if self.color_grad is not None else None
+            ro, rd, d, col, ii, jj, radius = self._keyframe_rays(k, stride=self.add_stride,
+                                                                 radius_map=rmaps[0] if rmaps else None)
             npc.add_neural_points(ro, rd, d, col, k, ii, jj, dynamic_radius=radius)
+            if self.pixels_based_on_color_grad > 0:
+                self._anchor_grad_points(k, rmaps)
         if npc.pts_num() == 0:
             return None
         geo = npc.geo_feats.detach().clone().requires_grad_(True)
@@ -185,6 +213,11 @@ class SequenceRunner:
                                            self.video.ht, self.video.wd, self.frustum_edge) \
                 if self.frustum_feature_selection else None
             row_masks = {id(geo): frustum[0], id(col_f): frustum[0]} if frustum is not None else None
+            # every window frame's own query radius map, built once per keyframe; the iteration gathers from them
+            rq = None
+            if rmaps is not None:
+                rq = {f: (rmaps[1] if f == k else self._radius_maps(f, win["views"][f], add=False)[1])
+                      for f in (win["window"] if win is not None else [k])}
             if win is None:
                 # every iteration's pixel draw in one transfer ([iteration][ii | jj][ray], the generator's order per iteration)
                 draws = torch.stack([torch.stack([torch.randint(0, self.video.wd, (self.map_rays,), generator=self.gen),
@@ -213,9 +246,10 @@ class SequenceRunner:
         def iteration():
             with torch.no_grad():
                 if win is None:
-                    ro, rd, d, gt_col, _, _, radius = self._keyframe_rays(k, view=view, pix=(pix[0], pix[1]))
+                    ro, rd, d, gt_col, _, _, radius = self._keyframe_rays(k, view=view, pix=(pix[0], pix[1]),
+                                                                          radius_map=rq[k] if rq else None)
                 else:
-                    ro, rd, d, gt_col, radius = self._window_rays(win, pix)
+                    ro, rd, d, gt_col, radius = self._window_rays(win, pix, rq)
             opt.zero_grad()
             depth, _, colour, _, counts = ren.render_batch_ray(npc, dec, rd, ro, self.device, "color", gt_depth=d,
                                                                npc_geo_feats=geo, npc_col_feats=col_f,
@@ -235,7 +269,8 @@ class SequenceRunner:
             if self.map_probe is not None and not torch.cuda.is_current_stream_capturing():
                 self.map_probe(k, dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(), colour=colour.detach(),
                                        seen=seen, loss=loss.detach(), warp=warp, window=win,
-                                       frustum=frustum[0] if frustum is not None else None))
+                                       frustum=frustum[0] if frustum is not None else None, radius=radius,
+                                       pix=pix))
             loss.backward()
             opt.step(row_masks=row_masks)
             return loss.detach()
@@ -327,15 +362,42 @@ class SequenceRunner:
                             "value": torch.zeros((), device=self.device), "first": None})
             return win
 
-    def _window_rays(self, win, pix):
-        """the rays of one iteration over the window: frame f's slice of `pix` through its own view, depth and image"""
+    def _window_rays(self, win, pix, rq=None):
+        """the rays of one iteration over the window: frame f's slice of `pix` through its own view, depth and image
+        (and its own query radius map of `rq`, frame -> [H,W], when given)"""
         per, parts = win["per"], []
         for i, f in enumerate(win["window"]):
             sl = slice(i * per, (i + 1) * per)
-            parts.append(self._keyframe_rays(f, view=win["views"][f], pix=(pix[0, sl], pix[1, sl])))
+            parts.append(self._keyframe_rays(f, view=win["views"][f], pix=(pix[0, sl], pix[1, sl]),
+                                             radius_map=rq[f] if rq else None))
         ro, rd, d, col = (torch.cat([p[j] for p in parts]) for j in range(4))
         radius = torch.cat([p[6] for p in parts]) if parts[0][6] is not None else None
         return ro, rd, d, col, radius
+
+    def _radius_maps(self, f, view, add=True):
+        """(dynamic_r_add / 3 * depth or None, dynamic_r_query / 3 * depth) [H,W] of keyframe f from its image and the
+        depth of `view` (mapper.py:538, :719, :767-784): one launch"""
+        m = color_grad_maps(self.images[f], depth_add=view[0] if add else None, depth_query=view[0],
+                            outputs=("r_add", "r_query") if add else ("r_query",), **self.color_grad)
+        return m.get("r_add"), m["r_query"]
+
+    def _anchor_grad_points(self, k, rmaps):
+        """the second anchoring pass (mapper.py:312-322): pixels_based_on_color_grad pixels drawn from the 5x as many of
+        highest colour gradient where the keyframe has depth, inserted with is_pts_grad=True"""
+        ren, H, W = self.renderer, self.video.ht, self.video.wd
+        depth, c2w = self._keyframe_view(k)
+        color = self.images[k].permute(1, 2, 0)
+        ro, rd, d, col, ii, jj = get_samples_with_pixel_grad(0, H, 0, W, self.pixels_based_on_color_grad, H, W, ren.fx,
+                                                             ren.fy, ren.cx, ren.cy, c2w, depth, color, self.device,
+                                                             depth > 0, generator=self.gen)
+        if rmaps is not None:
+            radius = rmaps[0][jj, ii]
+        elif self.npc.use_dynamic_radius:
+            radius = torch.full_like(d, 0.5 * (self.npc.radius_add + self.npc.radius_query))
+        else:
+            radius = None
+        self.npc.add_neural_points(ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous(), d, col.contiguous(),
+                                   k, ii, jj, is_pts_grad=True, dynamic_radius=radius)
 
     def _capture_iteration(self, iteration):
         """record one mapping iteration into a hipGraph (one memory pool for all keyframes of this runner, kept open by a

@@ -809,6 +809,29 @@ int glorie_keyframe_overlap(const float* rays_o, const float* rays_d, const floa
                             const float* c2ws, int K, float fx, float fy, float cx, float cy, int H, int W, float edge,
                             int* inside, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Colour-gradient radii and the gradient-ranked pixel draw of the mapper                */
+/* ------------------------------------------------------------------------------------ */
+
+/* Mapper.run's dynamic radius maps and get_sample_uv_with_grad's magnitude   reference: src/mapper.py:767-784,
+ * src/utils/common.py:96-118.  image f32 [H,W,3] (channels_first 0) or [3,H,W] (channels_first 1); valid [H,W] u8 or
+ * NULL.  Gray = rgb . [0.2125, 0.7154, 0.0721] in fp32; Sobel = scipy.ndimage.convolve with [1,0,-1] x [1,2,1]/4,
+ * mode='reflect' (index -1 reads 0, index H reads H-1; borders not zeroed), summed in double and rounded once;
+ * grad = sqrt(gx^2 + gy^2) in fp32, -1 where valid is 0.  r_add = interp1d([0, 0.01, thr], [rmax, rmax, rmin]) of the
+ * magnitude clipped to [0, float32(thr)], in double, times depth_add / 3 when depth_add [H,W] is given; r_query likewise
+ * with rmax, rmin times radius_query_ratio and depth_query.  Each output [H,W] f32 is written only when not NULL.
+ * thr <= 0.01 is GLORIE_EINVAL (interp1d's nodes must increase).  One launch. */
+int glorie_color_grad_maps(const float* image, int H, int W, int channels_first, const unsigned char* valid,
+                           double color_grad_threshold, double radius_add_max, double radius_add_min,
+                           double radius_query_ratio, const float* depth_add, const float* depth_query, float* grad,
+                           float* r_add, float* r_query, void* stream);
+/* The M largest of n f32 keys as int64 linear indices in ascending order (indices [M]); equal keys at the boundary go to
+ * the lowest indices.  valid_count[0] int32 = number of selected keys >= 0.  M > n is GLORIE_EINVAL (np.argpartition
+ * raises); M = 0 writes valid_count 0 only.  workspace: glorie_topm_workspace(n) bytes.  12 launches whatever the data,
+ * integer counts only (bitwise repeatable), no host synchronisation. */
+size_t glorie_topm_workspace(int n);
+int glorie_topm(const float* keys, int n, int M, void* workspace, int64_t* indices, int* valid_count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
