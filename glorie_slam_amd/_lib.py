@@ -120,6 +120,11 @@ SIGNATURES = {
     "glorie_color_grad_maps": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp] + [ctypes.c_double] * 4 + [_vp] * 6),
     "glorie_topm_workspace": (_sz, [_c_int]),
     "glorie_topm": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "glorie_npc_deform_workspace": (_sz, [_c_int]),
+    "glorie_npc_deform": (_c_int, [_vp] * 4 + [_c_int] * 3 + [_vp] * 5 + [ctypes.c_long, _vp, ctypes.c_long, _c_int]
+                          + [_c_f, _c_f, _c_int] + [_c_f] * 4 + [_vp, _vp, _vp]),
+    "glorie_iproj_dirty": (_c_int, [_vp] * 5 + [_c_int] * 3 + [_vp, _vp, _c_int, _vp]),
+    "glorie_proxy_depth": (_c_int, [_vp, _vp] + [_c_int] * 4 + [_vp] + [_c_f] * 4 + [_vp] * 5),
 }
 
 _lib = None

@@ -166,16 +166,7 @@ __global__ __launch_bounds__(256) void iproj_kernel(
   const Pose g = load_pose(poses + b * 7);
   if (k >= HW) return;
   const int y = k / w, x = k - y * w;
-  float Xi[4], Xj[4];
-  Xi[0] = ((float)x - cx) / fx;
-  Xi[1] = ((float)y - cy) / fy;
-  Xi[2] = 1.0f;
-  Xi[3] = disps[(size_t)b * HW + k];
-  se3_act(g, Xi, Xj);
-  float* o = points + ((size_t)b * HW + k) * 3;
-  o[0] = Xj[0] / Xj[3];
-  o[1] = Xj[1] / Xj[3];
-  o[2] = Xj[2] / Xj[3];
+  iproj_pixel(g, x, y, disps[(size_t)b * HW + k], fx, fy, cx, cy, points + ((size_t)b * HW + k) * 3);
 }
 
 // depth_filter: the reference launches (num, 6, chunks) blocks and atomically adds 1.0 per

@@ -393,3 +393,94 @@ def update_points_pos(npc, video, mono_depth_loader=None):
         npc.update_points_pos(v_idx, render_depth.clone(), c2w.clone(), video.cfg)
     npc.add_points(video_idx)
     npc.retrain_updated_points()
+
+
+# ---- the same two steps on HIP (csrc/deform.hip): every dirty keyframe in one call, no host round trip ------------------
+def deform_points(npc, video, fx, fy, cx, cy, stats=None, rebuild_index=True):
+    """update_points_pos(npc, video) of the "proxy" render depth (neural_point.py:509-537) in six launches: every input
+    point of a keyframe whose `npc_dirty` flag is set is re-placed from the keyframe's current pose and depth
+    (glorie_npc_deform), the keyframes' unprojected maps are refreshed (glorie_iproj_dirty, = add_points(idx)), the flags
+    are cleared, and the search structure is rebuilt (retrain_updated_points).  fx, fy, cx, cy: the renderer's
+    intrinsics (the reference's update_cam(cfg)).  An empty cloud returns False and leaves the flags set, as the reference
+    does.  Deviation: a dirty keyframe none of whose points has a valid depth keeps scale 1 (the reference writes NaN).
+    stats: an int64 device tensor [2] that accumulates (dirty keyframes seen, points moved) without a host read.
+    rebuild_index=False issues the launches only (what a hipGraph records); the caller rebuilds the index."""
+    if npc.pts_num() == 0:
+        return False
+    B, H, W = video.disps_up.shape
+    dev = video.disps_up.device
+    if npc._full_pcl is None:
+        npc._full_pcl = torch.zeros(B, H, W, 3, device=dev, dtype=torch.float)
+        npc._full_mask = torch.zeros(B, H, W, device=dev, dtype=torch.bool)
+    n = npc._input_pos.shape[0] if npc._input_pos is not None else 0
+    idx = [npc._input_video_idx, npc._input_j, npc._input_i]
+    if n and any(t.dtype != torch.int64 for t in idx):
+        raise TypeError("deform_points needs int64 input indices")
+    for name, t in (("input_depth", npc._input_depth), ("input_pos", npc._input_pos), ("cloud_pos", npc._cloud_pos)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError(f"{name} must be contiguous float32")
+    L.need_cuda(video.disps_up, npc._cloud_pos)
+    lib = L.load()
+    dirty = video.npc_dirty.view(torch.uint8)
+    valid = video.valid_depth_mask.view(torch.uint8)
+    poses = video.poses.detach().contiguous()
+    disps_up = video.fresh_disps_up().detach().contiguous()
+    ws = torch.empty(max(int(lib.glorie_npc_deform_workspace(B)), 8), dtype=torch.uint8, device=dev)
+    moved = stats[1:2] if stats is not None else None
+    if stats is not None:
+        stats[0:1] += video.npc_dirty.sum()
+    L.check(lib.glorie_npc_deform(L.ptr(poses), L.ptr(disps_up), L.ptr(valid), L.ptr(dirty), B, H, W,
+                                  L.ptr(idx[0] if n else None), L.ptr(idx[1] if n else None),
+                                  L.ptr(idx[2] if n else None), L.ptr(npc._input_depth if n else None),
+                                  L.ptr(npc._input_pos if n else None), n, L.ptr(npc._cloud_pos), npc._cloud_pos.shape[0],
+                                  int(npc.N_add), float(npc.near_end_surface), float(npc.far_end_surface),
+                                  int(bool(npc.fix_interval_when_add_along_ray)), float(fx), float(fy), float(cx),
+                                  float(cy), L.ptr(ws), L.ptr(moved), L.stream_ptr()), "glorie_npc_deform")
+    iproj_dirty(npc, video, clear_flags=True)
+    if rebuild_index:
+        npc.retrain_updated_points()
+    return True
+
+
+def iproj_dirty(npc, video, clear_flags=True):
+    """add_points(idx) of every keyframe whose npc_dirty flag is set (glorie_iproj_dirty), then (clear_flags) clear them"""
+    B, H, W = video.disps_up.shape
+    inv = se3_inv(video.poses.detach())                                    # as _add_video_points forms it
+    intr = (video.intrinsics[0].detach() * float(video.down_scale)).contiguous()
+    L.check(L.load().glorie_iproj_dirty(L.ptr(inv), L.ptr(video.fresh_disps_up().detach().contiguous()), L.ptr(intr),
+                                        L.ptr(video.valid_depth_mask.view(torch.uint8)),
+                                        L.ptr(video.npc_dirty.view(torch.uint8)), B, H, W, L.ptr(npc._full_pcl),
+                                        L.ptr(npc._full_mask.view(torch.uint8)), int(bool(clear_flags)), L.stream_ptr()),
+            "glorie_iproj_dirty")
+
+
+def proxy_skip_row(counter, mapping_window_size, H):
+    """the image row that `full_mask[:, counter - mapping_window_size] = 0` zeroes in every keyframe (neural_point.py:468),
+    negative values wrapped as Python indexing wraps them; -1 where the reference raises IndexError (outside [-H, H))"""
+    r = int(counter) - int(mapping_window_size)
+    return r % H if -H <= r < H else -1
+
+
+def proxy_render_depth(npc, video, c2w, droid_depth, mono_depth, mapping_window_size, fx, fy, cx, cy,
+                       use_mono_to_complete=True):
+    """get_proxy_render_depth (neural_point.py:539-575) over proj_depth_map of the unprojected keyframe maps: the
+    tracker's depth where > 0, else the nearest point of full_pcl[0, counter) projected into `c2w` (OpenGL convention),
+    else (use_mono_to_complete) the aligned mono prior.  Follows the reference's mask: image row counter -
+    mapping_window_size of every keyframe is left out (proxy_skip_row); proj_depth_map of this module drops a whole
+    keyframe instead.  Three launches (glorie_proxy_depth), no host synchronisation.  -> [H,W] f32"""
+    H, W = droid_depth.shape
+    dev = droid_depth.device
+    droid = droid_depth.detach().to(torch.float32).contiguous()
+    mono = mono_depth.detach().to(torch.float32).contiguous() if use_mono_to_complete else None
+    counter = int(video.counter.value) if npc._full_pcl is not None else 0
+    if npc._full_pcl is not None:
+        counter = min(counter, npc._full_pcl.shape[0])
+    w2c = torch.linalg.inv_ex(c2w.detach().to(dev, torch.float32))[0].contiguous()    # (inv_ex: no host check)
+    zbuf = torch.empty(H, W, device=dev, dtype=torch.float32)
+    out = torch.empty(H, W, device=dev, dtype=torch.float32)
+    L.check(L.load().glorie_proxy_depth(L.ptr(npc._full_pcl if counter else None),
+                                        L.ptr(npc._full_mask.view(torch.uint8) if counter else None), counter, H, W,
+                                        proxy_skip_row(video.counter.value, mapping_window_size, H), L.ptr(w2c),
+                                        float(fx), float(fy), float(cx), float(cy), L.ptr(droid), L.ptr(mono),
+                                        L.ptr(zbuf), L.ptr(out), L.stream_ptr()), "glorie_proxy_depth")
+    return out

@@ -22,9 +22,20 @@ from .common import get_rays_from_uv
 from .frontend import Frontend
 from .keyframe_select import frustum_feature_mask, keyframe_selection_overlap, random_select
 from .motion_filter import MotionFilter
-from .neural_point import se3_inv
+from .neural_point import deform_points, proxy_render_depth, se3_inv, update_points_pos
 from .render_train import FeatureAdam
 from .warp_loss import FrameTable, pix_warping_loss
+
+
+class _CfgVideo:
+    """a DepthVideo seen with another cfg (the torch deformation driver reads the render depth mode and the camera from
+    video.cfg); everything else is the video's own"""
+
+    def __init__(self, video, cfg):
+        self._video, self.cfg = video, cfg
+
+    def __getattr__(self, name):
+        return getattr(self._video, name)
 
 
 def pose_matrix(pose7):
@@ -47,7 +58,8 @@ class SequenceRunner:
     def __init__(self, net, video, cfg, npc, decoders, renderer, mono_depth_fn, use_graphs=True, ba_every=4, ba_steps=2,
                  map_iters=20, map_rays=1000, add_stride=8, seed=43, pix_warping=None, w_pix_warp_loss=None,
                  mapping_window_size=None, keyframe_selection_method=None, frustum_feature_selection=None,
-                 frustum_edge=None, color_grad_radius=None, pixels_based_on_color_grad=None):
+                 frustum_edge=None, color_grad_radius=None, pixels_based_on_color_grad=None, bind_npc_with_pose=None,
+                 render_depth=None, use_mono_to_complete=None):
         self.net, self.video, self.cfg = net, video, cfg
         self.npc, self.decoders, self.renderer = npc, decoders, renderer
         dev = cfg["device"]
@@ -112,6 +124,25 @@ class SequenceRunner:
         # the constructor argument; 0 is off
         self.pixels_based_on_color_grad = int(mp.get("pixels_based_on_color_grad", 0)
                                               if pixels_based_on_color_grad is None else pixels_based_on_color_grad)
+        # deformation of the cloud after tracker updates (mapper.py:705-707) and the depth the mapper trains on
+        # (mapper.py:246-279, :557-573, :713-730): cfg["pointcloud"]["bind_npc_with_pose"], cfg["mapping"]["render_depth"]
+        # ("proxy" / "mono") and ["use_mono_to_complete"], or the constructor arguments.  Off, the view depth stays
+        # 1 / disps_up and nothing is deformed
+        self.bind_npc_with_pose = bool(pc.get("bind_npc_with_pose", False) if bind_npc_with_pose is None
+                                       else bind_npc_with_pose)
+        mode = mp.get("render_depth") if render_depth is None else render_depth
+        if mode not in (None, False, "", "proxy", "mono"):
+            raise ValueError(f"render_depth must be 'proxy' or 'mono', got {mode!r}")
+        self.render_depth = mode or None
+        self.use_mono_to_complete = bool(mp.get("use_mono_to_complete", True) if use_mono_to_complete is None
+                                         else use_mono_to_complete)
+        self.mono_depth_fn = mono_depth_fn
+        self.mono_priors = {}                 # keyframe -> its mono prior (keyframe_dict['mono_depth'])
+        self._mono_by_tstamp = {}             # timestamp -> mono prior (device, [H,W] f32: 1.2 MB at 640x480)
+        self.skipped = []                     # keyframes not mapped: fewer than 100 valid tracker depths
+        self.deform_stats = {"calls": 0, "dirty_keyframes": 0, "points_moved": 0}
+        self._deform_counts = None            # device int64 [dirty keyframes, points moved], read once per keyframe
+        self._render_views = None             # inside map_keyframe with render_depth: frame -> (depth, c2w) or None
 
     # ---- tracker.py:33-77 ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -141,7 +172,10 @@ class SequenceRunner:
 
     # ---- mapper.py:517-684 (one keyframe) ---------------------------------------------------------------------------
     def _keyframe_view(self, k):
-        """depth map and camera-to-world matrix of keyframe k (constant while the keyframe is mapped)"""
+        """depth map and camera-to-world matrix of keyframe k (constant while the keyframe is mapped); with render_depth,
+        inside map_keyframe, the render depth of the frames computed for it (_render_view)"""
+        if self._render_views is not None and self._render_views.get(k) is not None:
+            return self._render_views[k]
         v = self.video
         depth = torch.where(v.disps_up[k] > 0, 1.0 / v.disps_up[k].clamp_min(1e-6), torch.zeros_like(v.disps_up[k]))
         c2w = pose_matrix(se3_inv(v.poses[k]))
@@ -185,18 +219,40 @@ class SequenceRunner:
         mapper.py:497-505; learning rates of the colour stage, mapper.py:412-414).  With pix_warping on or a
         keyframe_selection_method, the rays are split over a window of keyframes (_map_window); with pix_warping the
         pixel-warping term joins the loss (warp_loss.py).  With frustum_feature_selection only the feature rows inside
-        the keyframe's frustum are trained (keyframe_select.py; FeatureAdam's row masks)"""
+        the keyframe's frustum are trained (keyframe_select.py; FeatureAdam's row masks).  With bind_npc_with_pose the
+        cloud is deformed first; with render_depth the keyframe is inserted on its anchor depth and every window frame
+        trains on its render depth (proxy or aligned mono), and a frame with too few tracker depths is skipped"""
         npc, dec, ren = self.npc, self.decoders, self.renderer
-        with torch.no_grad():
-            # colour-gradient radii of k scaled by its depth: (r_add, r_query) [H,W], or None
-            rmaps = self._radius_maps(k, self._keyframe_view(k)) if self.color_grad is not None else None
-            ro, rd, d, col, ii, jj, radius = self._keyframe_rays(k, stride=self.add_stride,
-                                                                 radius_map=rmaps[0] if rmaps else None)
-            npc.add_neural_points(ro, rd, d, col, k, ii, jj, dynamic_radius=radius)
-            if self.pixels_based_on_color_grad > 0:
-                self._anchor_grad_points(k, rmaps)
-        if npc.pts_num() == 0:
-            return None
+        self._render_views = None
+        try:
+            with torch.no_grad():
+                if self.bind_npc_with_pose and npc.pts_num() > 0:
+                    self._deform()
+                anchor = None
+                if self.render_depth is not None:
+                    anchor = self._prepare_render(k)
+                    if anchor is None:
+                        self.skipped.append(k)
+                        return None
+                # colour-gradient radii of k scaled by its depth: (r_add, r_query) [H,W], or None
+                ins_view = anchor if anchor is not None else self._keyframe_view(k)
+                query_depth = self._keyframe_view(k)[0] if anchor is not None else None
+                rmaps = self._radius_maps(k, ins_view, query_depth=query_depth) if self.color_grad is not None else None
+                ro, rd, d, col, ii, jj, radius = self._keyframe_rays(k, stride=self.add_stride, view=ins_view,
+                                                                     radius_map=rmaps[0] if rmaps else None)
+                npc.add_neural_points(ro, rd, d, col, k, ii, jj, dynamic_radius=radius)
+                if self.pixels_based_on_color_grad > 0:
+                    self._anchor_grad_points(k, rmaps, view=ins_view)
+            if npc.pts_num() == 0:
+                return None
+            return self._optimize_keyframe(k, rmaps)
+        finally:
+            self._render_views = None
+            self._read_deform_stats()
+
+    def _optimize_keyframe(self, k, rmaps):
+        """the mapping iterations of map_keyframe (after the insertion)"""
+        npc, dec, ren = self.npc, self.decoders, self.renderer
         geo = npc.geo_feats.detach().clone().requires_grad_(True)
         col_f = npc.col_feats.detach().clone().requires_grad_(True)
         dec.train()
@@ -329,6 +385,96 @@ class SequenceRunner:
             self.frustum_counts.append(int(frustum[1]))
         return self.losses[-1]
 
+    # ---- deformation and render depth (mapper.py:246-279, :557-573, :705-730) -------------------------------------
+    def _deform(self):
+        """update_points_pos(npc, video) of the reference: on HIP (deform_points) unless render_depth is "mono", where the
+        torch driver re-places the points with the mono priors of the dirty keyframes (computed first where missing).
+        Like the reference, nothing happens when no flag is set (one host read of the flags: no index rebuild then)"""
+        npc, v, ren = self.npc, self.video, self.renderer
+        if npc.video is None:
+            npc.video = v
+        if not bool(v.npc_dirty.any()):
+            return
+        if self._deform_counts is None:
+            self._deform_counts = torch.zeros(2, dtype=torch.int64, device=self.device)
+        if self.render_depth == "mono":
+            dirty, = torch.where(v.npc_dirty)
+            # the driver asks for every dirty keyframe's prior by dataset index, the ones without points included
+            priors = {int(v.timestamp[f]): self._mono_prior(f) for f in dirty.tolist()}
+            self._deform_counts[0] += dirty.numel()
+            if npc._input_video_idx is not None:
+                self._deform_counts[1] += torch.isin(npc._input_video_idx, dirty).sum()
+            update_points_pos(npc, _CfgVideo(v, self._mono_cfg()), priors.__getitem__)
+            self.deform_stats["calls"] += 1
+            return
+        if deform_points(npc, v, ren.fx, ren.fy, ren.cx, ren.cy, stats=self._deform_counts):
+            self.deform_stats["calls"] += 1
+
+    def _mono_cfg(self):
+        """the runner's cfg with what the torch deformation driver reads from video.cfg: the render depth mode and the
+        renderer's camera as update_cam expects it"""
+        v, ren = self.video, self.renderer
+        cam = dict(self.cfg.get("cam", {}))
+        cam.update(H=v.ht, W=v.wd, H_out=v.ht, W_out=v.wd, H_edge=0, W_edge=0, fx=ren.fx, fy=ren.fy, cx=ren.cx, cy=ren.cy)
+        return dict(self.cfg, cam=cam, mapping=dict(self.cfg.get("mapping", {}), render_depth="mono"))
+
+    def _read_deform_stats(self):
+        if self._deform_counts is not None:
+            dirty, moved = self._deform_counts.tolist()
+            self.deform_stats.update(dirty_keyframes=int(dirty), points_moved=int(moved))
+
+    def _mono_prior(self, f):
+        """the mono prior of keyframe f, computed when it is first needed and kept (keyframe_dict['mono_depth']).  Kept by
+        timestamp: a keyframe of the tracker's window may still be culled and its slot reused by the next frame"""
+        ts = float(self.video.timestamp[f])
+        if ts not in self._mono_by_tstamp:
+            self._mono_by_tstamp[ts] = self.mono_depth_fn(ts, self.images.get(f)).to(self.device, torch.float32)
+        self.mono_priors[f] = self._mono_by_tstamp[ts]
+        return self.mono_priors[f]
+
+    def _frame_depths(self, f):
+        """Mapper.get_c2w_and_depth (mapper.py:246-279): (c2w in the OpenGL convention, aligned mono prior m_wq, tracker
+        depth with 0 outside valid_depth_mask), or None for fewer than 100 valid tracker depths (the reference means to
+        skip the frame there)"""
+        v = self.video
+        droid, valid, c2w = v.get_depth_and_pose(f, self.device)
+        if int(valid.sum()) < 100:
+            return None
+        droid[~valid] = 0
+        c2w[:3, 1:3] *= -1
+        m = self._mono_prior(f)
+        scale, shift = v.get_depth_scale_and_shift(f, m, droid, (m < m.mean() * 3) & valid)
+        return c2w, m * scale + shift, droid
+
+    def _render_depth_of(self, c2w, m_wq, droid):
+        if self.render_depth == "mono":
+            return m_wq
+        ren = self.renderer
+        return proxy_render_depth(self.npc, self.video, c2w, droid, m_wq, self.mapping_window_size, ren.fx, ren.fy,
+                                  ren.cx, ren.cy, use_mono_to_complete=self.use_mono_to_complete)
+
+    def _render_view(self, f):
+        """(render depth, c2w) of window frame f, None if it is skipped"""
+        rv = self._render_views
+        if f not in rv:
+            got = self._frame_depths(f)
+            rv[f] = None if got is None else (self._render_depth_of(*got), got[0])
+        return rv[f]
+
+    def _prepare_render(self, k):
+        """keyframe k with render_depth: its anchor view (insertion depth, c2w) - the tracker depth with holes from m_wq
+        in proxy mode, m_wq in mono mode - after add_points(k); its render view goes to _render_views.  None: skipped"""
+        got = self._frame_depths(k)
+        if got is None:
+            return None
+        c2w, m_wq, droid = got
+        anchor = torch.where(droid == 0, m_wq, droid) if self.render_depth == "proxy" else m_wq.clone()
+        if self.npc.video is None:
+            self.npc.video = self.video
+        self.npc.add_points(k)                          # full_pcl holds k before the projection (mapper.py:306)
+        self._render_views = {k: (self._render_depth_of(c2w, m_wq, droid), c2w)}
+        return anchor, c2w
+
     def _select_keyframes(self, k, view):
         """the keyframes of [0, k-1) that join k-1 and k in the window of keyframe k: up to mapping_window_size - 2 of
         them (mapper.py:541-549: the candidates are keyframe_dict[:-1]), by overlap with k's view or at random"""
@@ -351,8 +497,13 @@ class SequenceRunner:
         else:
             window = list(range(max(0, k - self.mapping_window_size + 1), k + 1))
         with torch.no_grad():
-            views = {f: (view if f == k else self._keyframe_view(f)) for f in window}
-            per = self.map_rays // len(window)
+            per = self.map_rays // len(window)          # (frames skipped below still count, mapper.py:584)
+            if self.render_depth is not None:
+                views = {f: (view if f == k else self._render_view(f)) for f in window}
+                window = [f for f in window if views[f] is not None]
+                views = {f: views[f] for f in window}
+            else:
+                views = {f: (view if f == k else self._keyframe_view(f)) for f in window}
             frame_ids = torch.tensor(window, dtype=torch.int64).to(self.device)
             win = {"window": window, "views": views, "per": per, "frame_ids": frame_ids,
                    "ray_frame": frame_ids.repeat_interleave(per)}
@@ -374,18 +525,19 @@ class SequenceRunner:
         radius = torch.cat([p[6] for p in parts]) if parts[0][6] is not None else None
         return ro, rd, d, col, radius
 
-    def _radius_maps(self, f, view, add=True):
+    def _radius_maps(self, f, view, add=True, query_depth=None):
         """(dynamic_r_add / 3 * depth or None, dynamic_r_query / 3 * depth) [H,W] of keyframe f from its image and the
-        depth of `view` (mapper.py:538, :719, :767-784): one launch"""
-        m = color_grad_maps(self.images[f], depth_add=view[0] if add else None, depth_query=view[0],
+        depth of `view` (mapper.py:538, :719, :767-784), the query radius from `query_depth` when given: one launch"""
+        m = color_grad_maps(self.images[f], depth_add=view[0] if add else None,
+                            depth_query=view[0] if query_depth is None else query_depth,
                             outputs=("r_add", "r_query") if add else ("r_query",), **self.color_grad)
         return m.get("r_add"), m["r_query"]
 
-    def _anchor_grad_points(self, k, rmaps):
+    def _anchor_grad_points(self, k, rmaps, view=None):
         """the second anchoring pass (mapper.py:312-322): pixels_based_on_color_grad pixels drawn from the 5x as many of
-        highest colour gradient where the keyframe has depth, inserted with is_pts_grad=True"""
+        highest colour gradient where the keyframe has depth, inserted with is_pts_grad=True (view: the anchor view)"""
         ren, H, W = self.renderer, self.video.ht, self.video.wd
-        depth, c2w = self._keyframe_view(k)
+        depth, c2w = view if view is not None else self._keyframe_view(k)
         color = self.images[k].permute(1, 2, 0)
         ro, rd, d, col, ii, jj = get_samples_with_pixel_grad(0, H, 0, W, self.pixels_based_on_color_grad, H, W, ren.fx,
                                                              ren.fy, ren.cx, ren.cy, c2w, depth, color, self.device,
@@ -441,6 +593,10 @@ class SequenceRunner:
         with torch.no_grad():
             n, n_edges = self.backend.dense_ba(final_ba_steps)             # the final global BA of slam.py / tracker.py
         self.map_pending()
+        if self.bind_npc_with_pose and self.npc.pts_num() > 0:
+            with torch.no_grad():                                           # the cloud follows the final trajectory
+                self._deform()
+            self._read_deform_stats()
         torch.cuda.synchronize()
         return {"keyframes": int(self.video.counter.value), "final_ba_edges": int(n_edges), "mapped": self.mapped,
                 "points": int(self.npc.pts_num()), "losses": list(self.losses), "timing": self.timing}

@@ -832,6 +832,45 @@ int glorie_color_grad_maps(const float* image, int H, int W, int channels_first,
 size_t glorie_topm_workspace(int n);
 int glorie_topm(const float* keys, int n, int M, void* workspace, int64_t* indices, int* valid_count, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Deformation of the point cloud and the proxy depth of the mapper                      */
+/* ------------------------------------------------------------------------------------ */
+
+/* update_points_pos(npc, video) for every keyframe whose npc_dirty flag is set, in one call
+ *   reference: src/neural_point.py:378-438 (NeuralPointCloud.update_points_pos), :509-537, :11-16 (get_scale);
+ *   src/depth_video.py:313-324 (get_pose, get_depth_and_pose); src/utils/common.py:39-54 (get_rays_from_uv)
+ * poses [B,7] world-to-camera, disps_up [B,H,W] f32, valid [B,H,W] u8 (valid_depth_mask), dirty [B] u8 (npc_dirty,
+ * read only).  Input point p (input_video_idx / input_j / input_i [n] int64) of a dirty keyframe v takes
+ * d = valid ? 1 / disps_up[v, j, i] : 0; d == 0 takes s_v * input_depth[p], s_v = sum(prev d) / sum(prev^2) over the
+ * points of v with d != 0 (int64 sums of the terms scaled by a per-keyframe power of two that keeps each sum below
+ * 2^61 whatever the depth range: bitwise repeatable; s_v = 1 when v has no such point, where the reference writes NaN).
+ * The ray of pixel (i, j) from the c2w of get_pose with columns 1 and 2 negated and the explicit intrinsics gives
+ * input_pos [n,3], input_depth [n] and the cloud rows p*n_add + s [cloud_rows,3]: z = near d (1 - t) + far d t,
+ * t = linspace(0, 1, n_add), or d + linspace(-0.04, 0.04, n_add) with fix_interval.
+ * cloud_rows != n * n_add is GLORIE_EINVAL.  workspace: glorie_npc_deform_workspace(B) bytes.  stats (NULL = none)
+ * [1] u64 += the number of points moved.  A memset and three launches, no host synchronisation. */
+size_t glorie_npc_deform_workspace(int B);
+int glorie_npc_deform(const float* poses, const float* disps_up, const uint8_t* valid, const uint8_t* dirty, int B,
+                      int H, int W, const int64_t* input_video_idx, const int64_t* input_j, const int64_t* input_i,
+                      float* input_depth, float* input_pos, long n, float* cloud_pos, long cloud_rows, int n_add,
+                      float near_end_surface, float far_end_surface, int fix_interval, float fx, float fy, float cx,
+                      float cy, void* workspace, unsigned long long* stats, void* stream);
+/* add_points(video_idxs) for every dirty keyframe   reference: src/neural_point.py:145-162
+ * inv_poses [B,7] = SE3(poses).inv().data of the whole table, intrinsics [4] (the full-resolution ones), full_pcl
+ * [B,H,W,3] and full_mask [B,H,W] u8: keyframe b is rewritten when dirty[b], with the device code of glorie_iproj
+ * (bitwise equal).  clear_flags != 0: a last launch sets dirty[0, B) to 0. */
+int glorie_iproj_dirty(const float* inv_poses, const float* disps_up, const float* intrinsics, const uint8_t* valid,
+                       uint8_t* dirty, int B, int H, int W, float* full_pcl, uint8_t* full_mask, int clear_flags,
+                       void* stream);
+/* get_proxy_render_depth over proj_depth_map(neural_pcl=False)   reference: src/neural_point.py:446-506, :539-575
+ * The points of full_pcl [>= counter,H,W,3] of keyframes [0, counter) where full_mask [.,H,W] u8 is set, except image
+ * row skip_row (in [0, H); -1 = none) of every keyframe, projected as glorie_proj_depth does with w2c [16] row-major;
+ * nearest point per pixel.  out [H,W] = droid_depth where > 0, else the projection where > 0, else (mono_depth != NULL)
+ * mono_depth where still 0.  zbuf [H,W] f32 scratch.  Three launches, no host synchronisation. */
+int glorie_proxy_depth(const float* full_pcl, const uint8_t* full_mask, int counter, int H, int W, int skip_row,
+                       const float* w2c, float fx, float fy, float cx, float cy, const float* droid_depth,
+                       const float* mono_depth, float* zbuf, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
