@@ -171,6 +171,27 @@ def ptr(t):
 BA_TARGETS_HWC = 2   # GLORIE_BA_TARGETS_HWC (include/glorie_hip.h)
 
 
+def f32(t):
+    """t as a contiguous float32 tensor (t itself when it already is one)"""
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
+
+
+def homogeneous(c2w):
+    """camera matrices [..,4,4] or [..,3,4] -> contiguous float32 [..,4,4] (a bottom row 0 0 0 1 appended)"""
+    c2w = f32(c2w)
+    if c2w.shape[-2:] == (3, 4):
+        bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], device=c2w.device).expand(*c2w.shape[:-2], 1, 4)
+        c2w = torch.cat([c2w, bottom], dim=-2).contiguous()
+    if c2w.shape[-2:] != (4, 4):
+        raise ValueError(f"camera matrices must be [..,4,4] or [..,3,4], got {tuple(c2w.shape)}")
+    return c2w
+
+
+def workspace(nbytes, device):
+    """uninitialised device bytes for a kernel's workspace (what its glorie_*_workspace function reports; never empty)"""
+    return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+
+
 def need_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:

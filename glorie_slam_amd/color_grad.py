@@ -21,10 +21,6 @@ from .common import get_rays_from_uv
 RADIUS_ADD_MAX, RADIUS_ADD_MIN, RADIUS_QUERY_RATIO, COLOR_GRAD_THRESHOLD = 0.08, 0.02, 2.0, 0.15
 
 
-def _f32(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
 def _layout(image):
     """[H,W,3] -> (H, W, 0); [3,H,W] -> (H, W, 1)"""
     if image.dim() == 3 and image.shape[-1] == 3:
@@ -46,10 +42,10 @@ def color_grad_maps(image, color_grad_threshold=COLOR_GRAD_THRESHOLD, radius_add
         if d is not None and tuple(d.shape) != (H, W):
             raise ValueError(f"{name} must be [{H},{W}], got {tuple(d.shape)}")
     out = {k: torch.empty(H, W, dtype=torch.float32, device=dev) for k in outputs}
-    img = _f32(image)
+    img = L.f32(image)
     v = valid.to(torch.uint8).contiguous() if valid is not None else None
-    da = _f32(depth_add) if depth_add is not None else None
-    dq = _f32(depth_query) if depth_query is not None else None
+    da = L.f32(depth_add) if depth_add is not None else None
+    dq = L.f32(depth_query) if depth_query is not None else None
     L.check(L.load().glorie_color_grad_maps(L.ptr(img), int(H), int(W), chw, L.ptr(v), float(color_grad_threshold),
                                             float(radius_add_max), float(radius_add_min), float(radius_query_ratio),
                                             L.ptr(da), L.ptr(dq), L.ptr(out.get("grad")), L.ptr(out.get("r_add")),
@@ -68,7 +64,7 @@ def top_indices(keys, M):
     """keys f32 [n] (any shape, flattened) on the device -> (indices int64 [M] ascending, valid int32 [1]): the M largest
     keys, equal keys at the boundary taken lowest index first; valid = how many of them are >= 0"""
     L.need_cuda(keys)
-    k = _f32(keys.reshape(-1))
+    k = L.f32(keys.reshape(-1))
     n = k.numel()
     if not 0 <= M <= n:
         raise ValueError(f"top_indices: M={M} outside [0, {n}] (np.argpartition raises)")
@@ -76,7 +72,7 @@ def top_indices(keys, M):
     lib = L.load()
     idx = torch.empty(M, dtype=torch.int64, device=dev)
     valid = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(int(lib.glorie_topm_workspace(n)), 8), dtype=torch.uint8, device=dev)
+    ws = L.workspace(lib.glorie_topm_workspace(n), dev)
     L.check(lib.glorie_topm(L.ptr(k), n, int(M), L.ptr(ws), L.ptr(idx), L.ptr(valid), L.stream_ptr(dev)), "glorie_topm")
     return idx, valid
 

@@ -18,8 +18,9 @@
 //   topm_scan_kernel         one workgroup: exclusive scans of the three counts, the valid count of the selection
 //   topm_write_kernel        every key above the threshold and the lowest-index `M - above` keys equal to it, written in
 //                            ascending index order
+// The float keys and the count, scan and rank steps are those of compact.hiph.
 // Every decision is an integer count: repeated calls are bitwise equal.
-#include "common.hiph"
+#include "compact.hiph"
 
 using namespace glorie;
 
@@ -29,7 +30,6 @@ constexpr int kTile = 16;                 // output tile edge
 constexpr int kHalo = kTile + 2;
 constexpr int kTopThreads = 256;
 constexpr int kTopWaves = kTopThreads / 64;
-constexpr int kScanThreads = 1024;
 constexpr int kHistItems = 8;             // keys per thread in a histogram pass
 
 struct RadiusMap {
@@ -110,12 +110,6 @@ color_grad_maps_kernel(const float* __restrict__ img, int H, int W, int chw, con
   }
 }
 
-// order-preserving unsigned key of a float (larger float -> larger key)
-__device__ __forceinline__ unsigned int float_key(float f) {
-  const unsigned int b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // state: [0] prefix of the threshold key, [1] rank still to skip from the top inside the prefix, [2] need (ties taken),
 // [3] -
 __global__ void __launch_bounds__(kTopThreads)
@@ -171,65 +165,34 @@ topm_count_kernel(const float* __restrict__ keys, int n, const unsigned int* __r
   const float f = i < n ? keys[i] : -1.f;
   const unsigned int k = float_key(f);
   const bool in = i < n;
-  const unsigned long long bg = __ballot(in && k > t), be = __ballot(in && k == t), bn = __ballot(in && f >= 0.f);
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = __popcll(bg);
-    red[1][threadIdx.x >> 6] = __popcll(be);
-    red[2][threadIdx.x >> 6] = __popcll(bn);
-  }
+  wave_count(in && k > t, red[0]);
+  wave_count(in && k == t, red[1]);
+  wave_count(in && f >= 0.f, red[2]);
   __syncthreads();
   if (threadIdx.x < 3) {
-    int c = 0;
-    for (int w = 0; w < kTopWaves; ++w) c += red[threadIdx.x][w];
-    (threadIdx.x == 0 ? cnt_gt : threadIdx.x == 1 ? cnt_eq : cnt_nonneg)[blockIdx.x] = c;
+    int* cnt = threadIdx.x == 0 ? cnt_gt : threadIdx.x == 1 ? cnt_eq : cnt_nonneg;
+    cnt[blockIdx.x] = slot_sum(red[threadIdx.x], kTopWaves);
   }
 }
 
 // one workgroup: exclusive scans of cnt_gt and cnt_eq in place; state[2] = M - (keys above the threshold);
 // valid[0] = min(M, keys >= 0)
 __global__ void __launch_bounds__(kScanThreads)
-topm_scan_kernel(int* __restrict__ cnt_gt, int* __restrict__ cnt_eq, const int* __restrict__ cnt_nonneg, int n_blocks,
-                 int M, unsigned int* __restrict__ state, int* __restrict__ valid) {
-  __shared__ int buf[2][kScanThreads];
-  __shared__ int carry[3];
+topm_scan_kernel(int* cnt_gt, int* cnt_eq, const int* __restrict__ cnt_nonneg, int n_blocks, int M,
+                 unsigned int* __restrict__ state, int* __restrict__ valid) {
   __shared__ int red[kScanThreads / 64];
-  const int tid = threadIdx.x;
-  if (tid < 3) carry[tid] = 0;
+  const int* const in[2] = {cnt_gt, cnt_eq};
+  int* const out[2] = {cnt_gt, cnt_eq};
+  int above_equal[2];
+  block_exclusive_scan<2>(in, out, n_blocks, above_equal);
+  int nn = 0;
+  for (int b = threadIdx.x; b < n_blocks; b += kScanThreads) nn += cnt_nonneg[b];
+  nn = wave_sum(nn);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nn;
   __syncthreads();
-  for (int base = 0; base < n_blocks; base += kScanThreads) {
-    const bool in = base + tid < n_blocks;
-    const int a = in ? cnt_gt[base + tid] : 0, e = in ? cnt_eq[base + tid] : 0;
-    int nn = in ? cnt_nonneg[base + tid] : 0;
-    buf[0][tid] = a;
-    buf[1][tid] = e;
-    __syncthreads();
-    for (int off = 1; off < kScanThreads; off <<= 1) {        // inclusive Hillis-Steele scans
-      const int xa = tid >= off ? buf[0][tid - off] : 0, xe = tid >= off ? buf[1][tid - off] : 0;
-      __syncthreads();
-      buf[0][tid] += xa;
-      buf[1][tid] += xe;
-      __syncthreads();
-    }
-    if (in) {
-      cnt_gt[base + tid] = carry[0] + buf[0][tid] - a;
-      cnt_eq[base + tid] = carry[1] + buf[1][tid] - e;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nn += __shfl_xor(nn, off, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = nn;
-    __syncthreads();
-    if (tid == 0) {
-      int s = 0;
-      for (int w = 0; w < kScanThreads / 64; ++w) s += red[w];
-      carry[0] += buf[0][kScanThreads - 1];
-      carry[1] += buf[1][kScanThreads - 1];
-      carry[2] += s;
-    }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    state[2] = (unsigned int)(M - carry[0]);
-    valid[0] = min(M, carry[2]);
+  if (threadIdx.x == 0) {
+    state[2] = (unsigned int)(M - above_equal[0]);
+    valid[0] = min(M, slot_sum(red, kScanThreads / 64));
   }
 }
 
@@ -240,30 +203,17 @@ topm_write_kernel(const float* __restrict__ keys, int n, const unsigned int* __r
   const unsigned int t = state[0];
   const int need = (int)state[2];
   const int i = blockIdx.x * kTopThreads + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned int k = i < n ? float_key(keys[i]) : 0u;
   const bool gt = i < n && k > t, eq = i < n && k == t;
-  const unsigned long long bg = __ballot(gt), be = __ballot(eq);
-  if (lane == 0) {
-    wg[wave] = __popcll(bg);
-    we[wave] = __popcll(be);
-  }
+  const unsigned long long bg = wave_count(gt, wg), be = wave_count(eq, we);
   __syncthreads();
-  int g = off_gt[blockIdx.x], e = off_eq[blockIdx.x];
-  for (int w = 0; w < wave; ++w) {
-    g += wg[w];
-    e += we[w];
-  }
-  const unsigned long long below = (1ull << lane) - 1ull;
-  g += __popcll(bg & below);
-  e += __popcll(be & below);
+  const int g = off_gt[blockIdx.x] + block_rank(bg, wg), e = off_eq[blockIdx.x] + block_rank(be, we);
   // position = selected keys of lower index: every key above the threshold, the first `need` ties
   const int pos = g + min(e, need);
   if ((gt || (eq && e < need)) && pos >= 0 && pos < M) out[pos] = i;
 }
 
 inline int top_blocks(int n) { return (n + kTopThreads - 1) / kTopThreads; }
-inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 RadiusMap make_map(double rmax, double rmin, double thr) {
   RadiusMap m;

@@ -17,12 +17,15 @@
 //                         keyframe's current c2w, and the input point plus its N_add cloud rows
 // glorie_iproj_dirty: iproj of every dirty keyframe (the device code of glorie_iproj) and a copy of its valid-depth mask,
 // then (optionally) a launch that clears the flags after everything else has read them.
-// glorie_proxy_depth: +inf fill, a z-buffer pass over the unprojected maps of keyframes [0, counter) (the projection of
-// proj_depth_map, atomicMin on the bit pattern of the positive depth), a finalize pass tracker -> projection -> mono.
+// glorie_proxy_depth: +inf fill, a z-buffer pass over the unprojected maps of keyframes [0, counter), a finalize pass
+// tracker -> projection -> mono.
+// The z-buffer pass (zbuf_kernel, launch_zbuf) is also the whole of glorie_proj_depth (render.hip): it lives here
+// because this unit compiles with contraction off, which the shared projection of camera.hiph then inherits.
 #include <hip/hip_runtime.h>
 // every fp32 operation rounded on its own, in the reference's order (as geom.hip): the unprojection is then bitwise
-// equal to glorie_iproj
+// equal to glorie_iproj, and the projection of the z-buffer pass keeps the bits it had in proj_depth_map
 #pragma clang fp contract(off)
+#include "camera.hiph"
 #include "common.hiph"
 #include "se3.hiph"
 
@@ -34,12 +37,6 @@ constexpr int kThreads = 256;
 
 // per-keyframe scratch of the scale: [0, 2B) the two int64 sums, then B int32 exponents (+ kExpBias), B uint32 counts
 constexpr int kExpBias = 4096;
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // keyframe of input point p if it is dirty and its pixel / keyframe indices are in range, else -1
 __device__ __forceinline__ int dirty_frame(const int64_t* __restrict__ vidx, const int64_t* __restrict__ pj,
@@ -92,11 +89,7 @@ __global__ __launch_bounds__(kThreads) void deform_range_kernel(
   const unsigned long long ballot = __ballot(has);
   const int v0 = __shfl(v, 0, 64);
   if (__all(v == v0)) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int other = __shfl_xor(e, o, 64);
-      e = other > e ? other : e;
-    }
+    e = glorie::wave_max(e);
     if ((threadIdx.x & 63) == 0 && v0 >= 0 && ballot) {
       atomicMax(&max_exp[v0], e);
       atomicAdd(&count[v0], (unsigned)__popcll(ballot));
@@ -132,8 +125,8 @@ __global__ __launch_bounds__(kThreads) void deform_scale_kernel(
   const int v0 = __shfl(v, 0, 64);
   const bool any_has = __any(has);
   if (__all(v == v0)) {
-    a = wave_sum_i64(a);
-    b = wave_sum_i64(b);
+    a = glorie::wave_sum(a);
+    b = glorie::wave_sum(b);
     if ((threadIdx.x & 63) == 0 && v0 >= 0 && any_has) {
       atomicAdd(&sums[2 * v0], (unsigned long long)a);
       atomicAdd(&sums[2 * v0 + 1], (unsigned long long)b);
@@ -251,26 +244,24 @@ __global__ __launch_bounds__(kThreads) void fill_inf_kernel(unsigned* __restrict
   if (k < n) bits[k] = 0x7f800000u;
 }
 
-// proj_depth_map over full_pcl[0, counter) masked by full_mask, without image row `skip_row` of every keyframe
-// (`full_mask[:, counter - mapping_window_size] = 0`; -1: no row)
-__global__ __launch_bounds__(kThreads) void proxy_zbuf_kernel(const float* __restrict__ pcl,
-                                                              const uint8_t* __restrict__ mask, long n, int H, int W,
-                                                              int skip_row, const float* __restrict__ w2c, float fx,
-                                                              float fy, float cx, float cy,
-                                                              unsigned* __restrict__ depth_bits) {
+// z-buffer projection of a point set into a pinhole view (neural_point.py:446-506, proj_depth_map): camera
+// coordinates X_c = w2c X (OpenGL convention: the camera looks along -z; the x axis is flipped before the
+// projection), pixel (u, v) = trunc(K X_c / z), depth = -z; the closest point per pixel wins.  The reference
+// sorts all points by depth and takes the first of every unique pixel; here every point does one atomicMin on
+// the bit pattern of its (positive) depth.  depth_bits must be pre-filled with +inf (0x7f800000).
+// mask: optional; skip_row: the points are the pixels of [.., H, W] maps and image row skip_row of every map is left
+// out (`full_mask[:, counter - mapping_window_size] = 0`; -1: no row)
+__global__ __launch_bounds__(kThreads) void zbuf_kernel(const float* __restrict__ pts, const uint8_t* __restrict__ mask,
+                                                        long n, int H, int W, int skip_row,
+                                                        const float* __restrict__ w2c, float fx, float fy, float cx,
+                                                        float cy, unsigned* __restrict__ depth_bits) {
   const long k = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (k >= n || !mask[k]) return;
-  if ((int)((k / W) % H) == skip_row) return;
-  const float x = pcl[k * 3 + 0], y = pcl[k * 3 + 1], z = pcl[k * 3 + 2];
-  float xc = w2c[0] * x + w2c[1] * y + w2c[2] * z + w2c[3];
-  const float yc = w2c[4] * x + w2c[5] * y + w2c[6] * z + w2c[7];
-  const float zc = w2c[8] * x + w2c[9] * y + w2c[10] * z + w2c[11];
-  xc = -xc;
-  const float zz = zc + 1e-6f;
-  const float u = (fx * xc + cx * zc) / zz, v = (fy * yc + cy * zc) / zz;
-  if (!(u < (float)W && u >= 0.0f && v < (float)H && v >= 0.0f && -zz > 0.0f)) return;
-  const int ui = (int)u, vi = (int)v;
-  atomicMin(&depth_bits[(size_t)vi * W + ui], __float_as_uint(-zz));
+  if (k >= n || (mask && !mask[k])) return;
+  if (skip_row >= 0 && (int)((k / W) % H) == skip_row) return;
+  const glorie::Proj p = glorie::project(w2c, pts[k * 3 + 0], pts[k * 3 + 1], pts[k * 3 + 2], fx, fy, cx, cy, 1e-6f);
+  if (!(p.u < (float)W && p.u >= 0.0f && p.v < (float)H && p.v >= 0.0f && -p.z > 0.0f)) return;
+  const int ui = (int)p.u, vi = (int)p.v;
+  atomicMin(&depth_bits[(size_t)vi * W + ui], __float_as_uint(-p.z));
 }
 
 // get_proxy_render_depth: the tracker's depth where > 0, else the projection where > 0, then (mono != NULL) the mono
@@ -291,6 +282,13 @@ __global__ __launch_bounds__(kThreads) void proxy_finalize_kernel(const unsigned
 }
 
 }  // namespace
+
+int glorie::launch_zbuf(const float* points, const uint8_t* mask, long n, int H, int W, int skip_row, const float* w2c,
+                        float fx, float fy, float cx, float cy, unsigned* depth_bits, hipStream_t st) {
+  hipLaunchKernelGGL(zbuf_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, points, mask, n,
+                     H, W, skip_row, w2c, fx, fy, cx, cy, depth_bits);
+  return check_launch();
+}
 
 extern "C" size_t glorie_npc_deform_workspace(int B) {
   return B > 0 ? (size_t)B * (2 * sizeof(unsigned long long) + sizeof(int) + sizeof(unsigned)) : 0;
@@ -357,11 +355,8 @@ extern "C" int glorie_proxy_depth(const float* full_pcl, const uint8_t* full_mas
   hipLaunchKernelGGL(fill_inf_kernel, grid_px, dim3(kThreads), 0, s, bits, HW);
   if (glorie::check_launch()) return GLORIE_EHIP;
   const long n = (long)counter * HW;
-  if (n > 0) {
-    hipLaunchKernelGGL(proxy_zbuf_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       full_pcl, full_mask, n, H, W, skip_row, w2c, fx, fy, cx, cy, bits);
-    if (glorie::check_launch()) return GLORIE_EHIP;
-  }
+  if (n > 0 && glorie::launch_zbuf(full_pcl, full_mask, n, H, W, skip_row, w2c, fx, fy, cx, cy, bits, s))
+    return GLORIE_EHIP;
   hipLaunchKernelGGL(proxy_finalize_kernel, grid_px, dim3(kThreads), 0, s, bits, droid_depth, mono_depth, HW, out);
   return glorie::check_launch();
 }

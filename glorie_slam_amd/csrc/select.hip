@@ -3,7 +3,8 @@
 //
 // Both take camera-to-world matrices in the renderer's OpenGL convention (what the reference passes after
 // `c2w[:3, 1:3] *= -1`) and invert the rigid transform in the kernel: w2c = [R^T | -R^T t].  A point projects as in the
-// reference: camera coordinates w2c . p, x negated, uv = K . cam, z = uv_z + 1e-5, uv = uv_xy / z.
+// reference: camera coordinates w2c . p, x negated, uv = K . cam, z = uv_z + 1e-5, uv = uv_xy / z (rigid_inverse,
+// project and inside_edge of camera.hiph; compiled here with the compiler's default contraction).
 //
 // Frustum selection, four launches and one memset, no host synchronisation (the count stays on the device):
 //   frustum_sample_kernel   one thread per point: project, sample the depth map bilinearly at (u, v) as
@@ -15,9 +16,11 @@
 //                           0 <= -z <= depth + 0.5; one kept count per workgroup (wave ballots, no atomics)
 //   select_scan_kernel      one workgroup: exclusive scan of the workgroup counts -> offsets and the total count
 //   frustum_indices_kernel  (only when indices are asked for) the kept points' indices in ascending order
+// The count, scan and rank steps are those of compact.hiph.
 // Overlap count, one launch: overlap_count_kernel, one workgroup per keyframe, an integer sum over the ray samples.
 // Every result is an integer decision or count: repeated calls are bitwise equal.
-#include "common.hiph"
+#include "camera.hiph"
+#include "compact.hiph"
 
 using namespace glorie;
 
@@ -25,41 +28,7 @@ namespace {
 
 constexpr int kSelThreads = 256;          // 4 waves of 64
 constexpr int kSelWaves = kSelThreads / 64;
-constexpr int kScanThreads = 1024;
-
-struct Rigid {
-  float r[12];                            // w2c, row-major 3x4
-};
-
-// w2c of a rigid c2w [4,4] row-major: R^T and -R^T t
-__device__ __forceinline__ Rigid rigid_inverse(const float* __restrict__ c2w) {
-  Rigid w;
-#pragma unroll
-  for (int row = 0; row < 3; ++row) {
-    const float a = c2w[0 + row], b = c2w[4 + row], c = c2w[8 + row];     // column `row` of R
-    w.r[row * 4 + 0] = a;
-    w.r[row * 4 + 1] = b;
-    w.r[row * 4 + 2] = c;
-    w.r[row * 4 + 3] = -(a * c2w[3] + b * c2w[7] + c * c2w[11]);
-  }
-  return w;
-}
-
-struct Proj {
-  float u, v, z;                          // z carries the + 1e-5
-};
-
-__device__ __forceinline__ Proj project(const float* w, float X, float Y, float Z, float fx, float fy, float cx,
-                                        float cy) {
-  const float a = w[0] * X + w[1] * Y + w[2] * Z + w[3];
-  const float b = w[4] * X + w[5] * Y + w[6] * Z + w[7];
-  const float c = w[8] * X + w[9] * Y + w[10] * Z + w[11];
-  Proj p;
-  p.z = c + 1e-5f;
-  p.u = (fx * (-a) + cx * c) / p.z;
-  p.v = (fy * b + cy * c) / p.z;
-  return p;
-}
+constexpr float kProjEps = 1e-5f;         // z + 1e-5 (mapper.py, common.py)
 
 __device__ __forceinline__ float depth_texel(const float* __restrict__ depth, int H, int W, int x, int y) {
   return (x < 0 || y < 0 || x >= W || y >= H) ? 0.f : depth[(size_t)y * W + x];
@@ -78,16 +47,6 @@ __device__ __forceinline__ float remap_linear(const float* __restrict__ depth, i
          depth_texel(depth, H, W, x0, y0 + 1) * w10 + depth_texel(depth, H, W, x0 + 1, y0 + 1) * w11;
 }
 
-// order-preserving unsigned key of a float (larger float -> larger key; 0 is below every key of a non-NaN float)
-__device__ __forceinline__ unsigned int float_key(float f) {
-  const unsigned int b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float key_float(unsigned int k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 __global__ void __launch_bounds__(kSelThreads)
 frustum_sample_kernel(const float* __restrict__ points, int n, const float* __restrict__ c2w, float fx, float fy,
                       float cx, float cy, int H, int W, float edge, const float* __restrict__ depth,
@@ -98,15 +57,13 @@ frustum_sample_kernel(const float* __restrict__ points, int n, const float* __re
   unsigned int key = 0;
   if (i < n) {
     const Proj p = project(w.r, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], fx, fy,
-                           cx, cy);
+                           cx, cy, kProjEps);
     const float s = remap_linear(depth, H, W, p.u, p.v);
-    const bool in = p.u < (float)W - edge && p.u > edge && p.v < (float)H - edge && p.v > edge;
-    zd[i] = make_float2(in ? -p.z : -INFINITY, s);
+    zd[i] = make_float2(inside_edge(p.u, p.v, H, W, edge) ? -p.z : -INFINITY, s);
     key = float_key(s);
   }
   // workgroup maximum, then one atomic per workgroup
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) key = max(key, (unsigned int)__shfl_xor((int)key, off, 64));
+  key = wave_max(key);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -129,40 +86,19 @@ frustum_mask_kernel(const float2* __restrict__ zd, int n, const unsigned int* __
     keep = 0.f <= e.x && e.x <= d + 0.5f;
     mask[i] = keep ? 1 : 0;
   }
-  const unsigned long long b = __ballot(keep);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = __popcll(b);
+  wave_count(keep, red);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int k = 0; k < kSelWaves; ++k) c += red[k];
-    block_count[blockIdx.x] = c;
-  }
+  if (threadIdx.x == 0) block_count[blockIdx.x] = slot_sum(red, kSelWaves);
 }
 
 // one workgroup: offsets[b] = sum of counts[0, b), total[0] = sum of all
 __global__ void __launch_bounds__(kScanThreads)
 select_scan_kernel(const int* __restrict__ counts, int n_blocks, int* __restrict__ offsets, int* __restrict__ total) {
-  __shared__ int buf[kScanThreads];
-  __shared__ int carry;
-  const int tid = threadIdx.x;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n_blocks; base += kScanThreads) {
-    const int v = base + tid < n_blocks ? counts[base + tid] : 0;
-    buf[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < kScanThreads; off <<= 1) {          // inclusive Hillis-Steele scan
-      const int add = tid >= off ? buf[tid - off] : 0;
-      __syncthreads();
-      buf[tid] += add;
-      __syncthreads();
-    }
-    if (base + tid < n_blocks) offsets[base + tid] = carry + buf[tid] - v;
-    __syncthreads();
-    if (tid == 0) carry += buf[kScanThreads - 1];
-    __syncthreads();
-  }
-  if (tid == 0) total[0] = carry;
+  const int* const in[1] = {counts};
+  int* const out[1] = {offsets};
+  int sum[1];
+  block_exclusive_scan<1>(in, out, n_blocks, sum);
+  if (threadIdx.x == 0) total[0] = sum[0];
 }
 
 __global__ void __launch_bounds__(kSelThreads)
@@ -170,14 +106,10 @@ frustum_indices_kernel(const unsigned char* __restrict__ mask, int n, const int*
                        int64_t* __restrict__ indices) {
   __shared__ int wave_base[kSelWaves];
   const int i = blockIdx.x * kSelThreads + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool keep = i < n && mask[i] != 0;
-  const unsigned long long b = __ballot(keep);
-  if (lane == 0) wave_base[wave] = __popcll(b);
+  const unsigned long long b = wave_count(keep, wave_base);
   __syncthreads();
-  int base = offsets[blockIdx.x];
-  for (int k = 0; k < wave; ++k) base += wave_base[k];
-  if (keep) indices[base + __popcll(b & ((1ull << lane) - 1ull))] = i;
+  if (keep) indices[offsets[blockIdx.x] + block_rank(b, wave_base)] = i;
 }
 
 // one workgroup per keyframe: samples z = near (1 - t) + far t of every ray with depth > 0 (near = 0.8 d, far = d + 0.5,
@@ -199,26 +131,20 @@ overlap_count_kernel(const float* __restrict__ rays_o, const float* __restrict__
     const float t = s < n_samples / 2 ? (float)s * step : 1.f - (float)(n_samples - 1 - s) * step;
     const float zs = (0.8f * d) * (1.f - t) + (d + 0.5f) * t;
     const Proj p = project(w.r, rays_o[3 * r] + rays_d[3 * r] * zs, rays_o[3 * r + 1] + rays_d[3 * r + 1] * zs,
-                           rays_o[3 * r + 2] + rays_d[3 * r + 2] * zs, fx, fy, cx, cy);
-    count += (p.u < (float)W - edge && p.u > edge && p.v < (float)H - edge && p.v > edge && p.z < 0.f) ? 1 : 0;
+                           rays_o[3 * r + 2] + rays_d[3 * r + 2] * zs, fx, fy, cx, cy, kProjEps);
+    count += (inside_edge(p.u, p.v, H, W, edge) && p.z < 0.f) ? 1 : 0;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
+  count = wave_sum(count);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = count;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int c = 0;
-    for (int k = 0; k < kSelWaves; ++k) c += red[k];
-    inside[blockIdx.x] = c;
-  }
+  if (threadIdx.x == 0) inside[blockIdx.x] = slot_sum(red, kSelWaves);
 }
 
 inline int sel_blocks(int n) { return (n + kSelThreads - 1) / kSelThreads; }
 
-// workspace layout: zd float2 [n] | block counts int [B] | offsets int [B] | max key uint (8-byte aligned pieces)
-inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
-
 }  // namespace
+
+// workspace layout: zd float2 [n] | block counts int [B] | offsets int [B] | max key uint (8-byte aligned pieces)
 
 extern "C" size_t glorie_frustum_select_workspace(int n) {
   if (n < 0) return 0;

@@ -1,7 +1,8 @@
 // Pixel-warping loss of the mapper (reference: src/mapper.py:326-388, projection src/utils/common.py:324-350).
 //
 // Every sampled ray's surface point X = o + d * depth is projected into the M frames of the mapping window; an entry
-// (ray r, frame m) is kept when the projection lands more than 5 px inside the image, in front of the camera, in a frame
+// (ray r, frame m) is kept when the projection (project of camera.hiph: common.py:336-350, uv = K p / (z + 1e-5),
+// compiled here with the compiler's default contraction) lands more than 5 px inside the image, in front of the camera, in a frame
 // other than the ray's own, and the ray has at least 4 such frames.  The kept entries' bilinear colour reads
 // (grid_sample, align_corners=False, border padding) are compared with the ray's colour under smooth-L1 (beta 0.1) and
 // averaged over 3 x the number of kept entries.
@@ -10,6 +11,7 @@
 // fixed-order partial per workgroup), pix_warp_finish_kernel (one workgroup: the partials in index order -> loss and the
 // gradient scale 1 / (3 count), both on the device), pix_warp_bwd_kernel (grad_depth = raw * g_out * scale).  No atomics:
 // repeated calls are bitwise identical, and nothing the host sizes depends on the data (the term records into a hipGraph).
+#include "camera.hiph"
 #include "common.hiph"
 
 using namespace glorie;
@@ -20,6 +22,7 @@ constexpr int kWarpThreads = 256;
 constexpr int kWarpMaxFrames = 64;        // one bit per frame in the per-ray mask
 constexpr int kWarpEdge = 5;              // pix_warping_edge (mapper.py:349)
 constexpr float kWarpBeta = 0.1f;         // smooth_l1_loss(..., beta=0.1) (mapper.py:385)
+constexpr float kProjEps = 1e-5f;
 
 // w2c = inverse of the affine c2w [4,4] (bottom row 0 0 0 1), row-major 3x4, inverted in double.  torch.inverse of the
 // reference agrees with it to fp32 rounding; a rigid c2w would allow R^T, the general form costs nothing here.
@@ -39,23 +42,6 @@ __device__ void affine_inverse(const float* c2w, float* w2c) {
     w2c[row * 4 + 2] = (float)R[row * 3 + 2];
     w2c[row * 4 + 3] = (float)(-(R[row * 3 + 0] * t0 + R[row * 3 + 1] * t1 + R[row * 3 + 2] * t2));
   }
-}
-
-struct WarpProj {
-  float a, b, c, zc, u, v;
-};
-
-// common.py:336-350: camera point (x negated before K), uv = K p / (z + 1e-5)
-__device__ __forceinline__ WarpProj warp_project(const float* w, float X, float Y, float Z, float fx, float fy, float cx,
-                                                 float cy) {
-  WarpProj p;
-  p.a = w[0] * X + w[1] * Y + w[2] * Z + w[3];
-  p.b = w[4] * X + w[5] * Y + w[6] * Z + w[7];
-  p.c = w[8] * X + w[9] * Y + w[10] * Z + w[11];
-  p.zc = p.c + 1e-5f;
-  p.u = (fx * (-p.a) + cx * p.c) / p.zc;
-  p.v = (fy * p.b + cy * p.c) / p.zc;
-  return p;
 }
 
 __device__ __forceinline__ float warp_texel(const float* img, int chw, int H, int W, int x, int y, int ch) {
@@ -92,10 +78,10 @@ pix_warp_fwd_kernel(const float* __restrict__ rays_o, const float* __restrict__ 
     const float X = ox + dx * dep, Y = oy + dy * dep, Z = oz + dz * dep;
     uint64_t mask = 0;
     if (isfinite(dep)) {            // a non-finite depth projects nowhere (every comparison of the reference is false)
+#pragma unroll 2                     // two frames per trip: their divisions overlap
       for (int m = 0; m < M; ++m) {
-        const WarpProj p = warp_project(w2c[m], X, Y, Z, fx, fy, cx, cy);
-        const bool in = p.u < (float)(W - kWarpEdge) && p.u > (float)kWarpEdge && p.v < (float)(H - kWarpEdge) &&
-                        p.v > (float)kWarpEdge && p.zc < 0.f && fid[m] != own;
+        const Proj p = project(w2c[m], X, Y, Z, fx, fy, cx, cy, kProjEps);
+        const bool in = inside_edge(p.u, p.v, H, W, (float)kWarpEdge) && p.z < 0.f && fid[m] != own;
         if (in) mask |= 1ull << m;
       }
     }
@@ -108,7 +94,7 @@ pix_warp_fwd_kernel(const float* __restrict__ rays_o, const float* __restrict__ 
     for (int m = 0; m < M; ++m) {
       if (!((mask >> m) & 1ull)) continue;
       const float* w = w2c[m];
-      const WarpProj p = warp_project(w, X, Y, Z, fx, fy, cx, cy);
+      const Proj p = project(w, X, Y, Z, fx, fy, cx, cy, kProjEps);
       // grid_sample's unnormalisation of u / W * 2 - 1 (align_corners=False), then the border clamp
       float ix = ((p.u / (float)W * 2.f - 1.f + 1.f) * (float)W - 1.f) * 0.5f;
       float iy = ((p.v / (float)H * 2.f - 1.f + 1.f) * (float)H - 1.f) * 0.5f;
@@ -120,12 +106,12 @@ pix_warp_fwd_kernel(const float* __restrict__ rays_o, const float* __restrict__ 
       const int x0 = (int)fx0, y0 = (int)fy0;
       const float e = ix - fx0, s = iy - fy0, we = (fx0 + 1.f) - ix, ws = (fy0 + 1.f) - iy;
       const float* img = frame_table ? frame_table[m] : images + (size_t)m * H * W * 3;
-      // d(a, b, c) / d depth = w2c_R . rays_d; u, v = (K row) . (-a, b, c) / zc
+      // d(a, b, c) / d depth = w2c_R . rays_d; u, v = (K row) . (-a, b, c) / z
       const float da = w[0] * dx + w[1] * dy + w[2] * dz;
       const float db = w[4] * dx + w[5] * dy + w[6] * dz;
       const float dc = w[8] * dx + w[9] * dy + w[10] * dz;
-      const float du = (-fx * da + cx * dc - p.u * dc) / p.zc;
-      const float dv = (fy * db + cy * dc - p.v * dc) / p.zc;
+      const float du = (-fx * da + cx * dc - p.u * dc) / p.z;
+      const float dv = (fy * db + cy * dc - p.v * dc) / p.z;
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) {
         const float vnw = warp_texel(img, chw, H, W, x0, y0, ch), vne = warp_texel(img, chw, H, W, x0 + 1, y0, ch);

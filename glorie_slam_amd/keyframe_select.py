@@ -21,20 +21,6 @@ from .common import get_rays_from_uv
 OVERLAP_EDGE = 20          # mapper.py:229
 
 
-def _f32(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
-def _c2w44(c2w):
-    c2w = _f32(c2w)
-    if c2w.shape[-2:] == (3, 4):
-        bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], device=c2w.device).expand(*c2w.shape[:-2], 1, 4)
-        c2w = torch.cat([c2w, bottom], dim=-2).contiguous()
-    if c2w.shape[-2:] != (4, 4):
-        raise ValueError(f"c2w must be [..,4,4] or [..,3,4], got {tuple(c2w.shape)}")
-    return c2w
-
-
 def frustum_feature_mask(points, c2w, depth, fx, fy, cx, cy, H, W, edge=-4, return_indices=False):
     """points [n,3], c2w [4,4] (or [3,4]), depth [H,W], all on the device -> (mask uint8 [n], count int32 [1]) without a
     host round trip; return_indices: also int64 [n] whose first `count` entries are the kept points in ascending order"""
@@ -47,8 +33,8 @@ def frustum_feature_mask(points, c2w, depth, fx, fy, cx, cy, H, W, edge=-4, retu
     mask = torch.empty(n, dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     indices = torch.empty(n, dtype=torch.int64, device=dev) if return_indices else None
-    ws = torch.empty(max(int(lib.glorie_frustum_select_workspace(n)), 8), dtype=torch.uint8, device=dev)
-    pts, c, dep = _f32(points), _c2w44(c2w), _f32(depth)
+    ws = L.workspace(lib.glorie_frustum_select_workspace(n), dev)
+    pts, c, dep = L.f32(points), L.homogeneous(c2w), L.f32(depth)
     L.check(lib.glorie_frustum_select(L.ptr(pts), n, L.ptr(c), float(fx), float(fy), float(cx), float(cy), int(H),
                                       int(W), float(edge), L.ptr(dep), L.ptr(ws), L.ptr(mask), L.ptr(count),
                                       L.ptr(indices), L.stream_ptr(dev)), "glorie_frustum_select")
@@ -72,13 +58,13 @@ def keyframe_overlap(rays_o, rays_d, depth, c2ws, fx, fy, cx, cy, H, W, n_sample
     reference's 0/0).  return_counts: (inside int32 [K], number of samples) instead"""
     L.need_cuda(rays_o, rays_d, depth, c2ws)
     R = depth.shape[0]
-    c = _c2w44(c2ws)
+    c = L.homogeneous(c2ws)
     if c.dim() != 3 or rays_o.shape != (R, 3) or rays_d.shape != (R, 3):
         raise ValueError("keyframe_overlap: rays_o, rays_d [R,3], depth [R], c2ws [K,4,4] expected")
     K = c.shape[0]
     dev = depth.device
     inside = torch.zeros(K, dtype=torch.int32, device=dev)
-    L.check(L.load().glorie_keyframe_overlap(L.ptr(_f32(rays_o)), L.ptr(_f32(rays_d)), L.ptr(_f32(depth)), R,
+    L.check(L.load().glorie_keyframe_overlap(L.ptr(L.f32(rays_o)), L.ptr(L.f32(rays_d)), L.ptr(L.f32(depth)), R,
                                              int(n_samples), L.ptr(c), K, float(fx), float(fy), float(cx), float(cy),
                                              int(H), int(W), float(edge), L.ptr(inside), L.stream_ptr(dev)),
             "glorie_keyframe_overlap")

@@ -425,7 +425,7 @@ def deform_points(npc, video, fx, fy, cx, cy, stats=None, rebuild_index=True):
     valid = video.valid_depth_mask.view(torch.uint8)
     poses = video.poses.detach().contiguous()
     disps_up = video.fresh_disps_up().detach().contiguous()
-    ws = torch.empty(max(int(lib.glorie_npc_deform_workspace(B)), 8), dtype=torch.uint8, device=dev)
+    ws = L.workspace(lib.glorie_npc_deform_workspace(B), dev)
     moved = stats[1:2] if stats is not None else None
     if stats is not None:
         stats[0:1] += video.npc_dirty.sum()

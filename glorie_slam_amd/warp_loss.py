@@ -24,8 +24,7 @@ class FrameTable:
     def __init__(self, images, channels_first=True):
         if not images:
             raise ValueError("FrameTable needs at least one image")
-        self.images = [im if (im.dtype == torch.float32 and im.is_contiguous()) else im.float().contiguous()
-                       for im in images]
+        self.images = [L.f32(im) for im in images]
         shape = self.images[0].shape
         for im in self.images:
             L.need_cuda(im)
@@ -40,19 +39,6 @@ class FrameTable:
         return len(self.images)
 
 
-def _f32(t):
-    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous()
-
-
-def _homogeneous(c2ws):
-    if c2ws.shape[-2:] == (4, 4):
-        return _f32(c2ws)
-    if c2ws.shape[-2:] == (3, 4):
-        bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], device=c2ws.device).expand(c2ws.shape[0], 1, 4)
-        return torch.cat([c2ws.float(), bottom], dim=1).contiguous()
-    raise ValueError(f"c2ws must be [M,4,4] or [M,3,4], got {tuple(c2ws.shape)}")
-
-
 class PixWarpLoss(torch.autograd.Function):
     """(depth, meta) -> (loss, count); gradient with respect to depth only"""
 
@@ -62,8 +48,8 @@ class PixWarpLoss(torch.autograd.Function):
         dev = depth.device
         N, M = depth.shape[0], c2ws.shape[0]
         lib = L.load()
-        depth_c = _f32(depth)
-        ws = torch.empty(max(int(lib.glorie_pix_warp_workspace(N)), 8), dtype=torch.uint8, device=dev)
+        depth_c = L.f32(depth)
+        ws = L.workspace(lib.glorie_pix_warp_workspace(N), dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         scale = torch.empty(1, dtype=torch.float32, device=dev)
         count = torch.empty(1, dtype=torch.int32, device=dev)
@@ -112,9 +98,9 @@ def pix_warping_loss(batch_rays_o, batch_rays_d, depth, c2ws, fx, fy, cx, cy, W,
         want = (M, 3, H, W) if channels_first else (M, H, W, 3)
         if tuple(img_gt_colors.shape) != want:
             raise ValueError(f"img_gt_colors must be {want}, got {tuple(img_gt_colors.shape)}")
-        images, table, chw = _f32(img_gt_colors), None, channels_first
-    meta = (_f32(batch_rays_o), _f32(batch_rays_d), indices_tensor.long().contiguous(), _homogeneous(c2ws),
-            frame_indices.long().contiguous(), images, table, chw, int(H), int(W), (fx, fy, cx, cy), _f32(batch_gt_color),
-            nan_to_zero)
+        images, table, chw = L.f32(img_gt_colors), None, channels_first
+    meta = (L.f32(batch_rays_o), L.f32(batch_rays_d), indices_tensor.long().contiguous(), L.homogeneous(c2ws),
+            frame_indices.long().contiguous(), images, table, chw, int(H), int(W), (fx, fy, cx, cy),
+            L.f32(batch_gt_color), nan_to_zero)
     loss, count = PixWarpLoss.apply(depth, meta)
     return (loss, count) if return_count else loss

@@ -4,7 +4,7 @@ csrc/color_grad.hip) and SequenceRunner's use of them (reference: src/mapper.py:
 
   * against the reference's own values (tests/golden/color_grad.npz, tests/golden/make_color_grad.py), both layouts;
   * the top-M selection against the restatement's (-key, index) order at 640x480 and 1200x680, with large ties, fewer
-    valid keys than M, M = n and no valid key;
+    valid keys than M, M = n and no valid key, and at flat sizes from one key to a few workgroups;
   * repeated calls bitwise equal, a recorded call replayed on new inputs equal to the eager call;
   * SequenceRunner with the radius keys (per-frame query radii, insertion radii, eager and recorded losses), with
     pixels_based_on_color_grad (an is_pts_grad=True insertion on the selected pixels), and without the keys."""
@@ -105,6 +105,17 @@ def test_top_m_matches_the_restatement(gpu, shape, kind):
         assert int(valid) == want_valid
     with pytest.raises(ValueError):
         top_indices(_t(keys, gpu), n + 1)
+    if kind not in ("random", "ties"):
+        return
+    # the sizes at which the count / scan / rank chain changes path: one key, a partial wave, one wave and one key more, a
+    # partial second workgroup, more than one workgroup (the two shapes above are past 1024 workgroups)
+    for m in (1, 63, 64, 65, 257, 2049):
+        small = _keys(kind, m, shape[0] + m)
+        for M in sorted({1, max(m // 2, 1), m}):
+            idx, valid = top_indices(_t(small, gpu), M)
+            want, want_valid = top_indices_ref(small, M)
+            assert np.array_equal(idx.cpu().numpy(), want), (kind, m, M)
+            assert int(valid) == want_valid, (kind, m, M)
 
 
 def test_repeat_and_replay(gpu):

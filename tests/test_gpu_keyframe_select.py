@@ -3,7 +3,8 @@ it (reference: src/mapper.py:126-244, :541-554, :591-621, :675-677).
 
   * against the reference's own values (tests/golden/keyframe_select.npz, tests/golden/make_keyframe_select.py);
   * against the float64 restatement (tests/keyframe_select_ref.py) at the product shape: the 524,286-point box cloud
-    seen by a 640x480 camera whose depth map has holes;
+    seen by a 640x480 camera whose depth map has holes, and at prefixes of it from one point to just past one chunk of
+    the scan;
   * repeated calls bitwise equal, the empty cases, an all-zero depth map, a recorded call replayed;
   * SequenceRunner with keyframe_selection_method "overlap" (windows of selected + [k-1, k], a turned-away keyframe never
     selected), with frustum_feature_selection (only rows inside the mask change, eager and recorded agree), and with the
@@ -90,6 +91,29 @@ def test_frustum_matches_the_restatement_at_the_product_shape(gpu):
         print(f"edge {edge}: kept {n} of {len(pts)}, restatement {int(ref.sum())}, differing {int(diff.sum())}")
         assert not (diff & ~near).any(), np.nonzero(diff & ~near)[0][:10]
         assert ref.sum() > 50000 and (~ref).sum() > 50000 and (d["sample"] == 0).any()
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1000, 262144, 262145, 263000])
+def test_frustum_matches_the_restatement_at_ragged_sizes(gpu, n):
+    """the first n points of a fixed permutation of the product cloud: one point, partial waves and workgroups, and the
+    first workgroups past one 1024-workgroup chunk of the scan (262144 points = 1024 workgroups of 256)"""
+    pts, c2w, depth, K, H, W = product_case()
+    pts = pts[np.random.default_rng(11).permutation(len(pts))[:n]]
+    for edge in (-4.0, 6.0):
+        mask, count, idx = _frustum(gpu, pts, c2w, depth, K, H, W, edge)
+        ref, d = frustum_ref(pts, c2w, depth, *K, H, W, edge)
+        assert mask.shape == (n,)
+        assert count == int(mask.sum()) and np.array_equal(idx, np.nonzero(mask)[0])
+        rel = lambda x, t: np.abs(x - t) <= 1e-4 * np.maximum(np.abs(t), 1.0)
+        q = lambda x: np.abs(x * 32 - np.floor(x * 32) - 0.5) < 1e-2          # a 1/32-px rounding boundary
+        near = rel(d["u"], edge) | rel(d["u"], W - edge) | rel(d["v"], edge) | rel(d["v"], H - edge) | \
+            rel(d["negz"], 0.0) | rel(d["negz"], d["depth"] + 0.5) | q(d["u"]) | q(d["v"])
+        diff = mask.astype(bool) != ref
+        print(f"n {n} edge {edge}: kept {count}, restatement {int(ref.sum())}, differing {int(diff.sum())}, "
+              f"near a threshold {near.mean():.4f}")
+        assert not (diff & ~near).any(), np.nonzero(diff & ~near)[0][:10]
+        if n >= 256:                                               # the band must not be what passes the test
+            assert near.mean() <= 0.05, near.mean()
 
 
 def test_repeated_calls_and_empty_cases(gpu):
