@@ -1,0 +1,223 @@
+"""Scenes with general rotations and a float64 reference of the projective-geometry operations (test infrastructure).
+
+The scenes of glorie_slam_amd/synth.py rotate about the y axis only (qx == qz == 0 exactly, qw > 0), share one intrinsics
+row and keep every reprojected point in front of the target camera.  The two scenes here do not:
+
+  general_graph  random rotation axes, angles up to 0.5 rad, every third quaternion negated (qw < 0), intrinsics that differ
+                 per frame and per component, and ~8 % of the pixels at disparity 2..6 - near points that land behind or
+                 close to the target camera, so that the Z < 0.1 clamp and the validity thresholds are exercised.
+  plane_graph    the same kind of poses looking at two world planes; the disparities come from float64 ray intersection,
+                 so the maps are multi-view consistent (what depth_filter and the bundle adjustment need).
+
+The references (reproject64, frame_distance64, iproj64, depth_filter64) work on 4 x 4 float64 matrices,
+Tij = T(pose_j) inv(T(pose_i)), with the rotation from scipy: they contain no quaternion sandwich formula and share nothing
+with oracle/se3.py beyond the pose layout [t | qx qy qz qw] (world -> camera).  Next to each result they return the float64
+quantities that the operations threshold, so that a test can tell a pixel that sits on a threshold from a wrong one.
+"""
+import numpy as np
+from scipy.spatial.transform import Rotation
+
+import glorie_slam_amd.synth as synth
+
+F = np.float32
+REL_BAND = 1e-4           # a float64 quantity within this relative distance of its threshold may round to either side
+
+
+def _edges(K, radius):
+    ii, jj = [], []
+    for i in range(K):
+        for j in range(K):
+            if i != j and (radius is None or abs(i - j) <= radius):
+                ii.append(i)
+                jj.append(j)
+    return np.array(ii, np.int64), np.array(jj, np.int64)
+
+
+def _random_poses(rng, K, ang_lo, ang_hi, tmax):
+    poses = np.zeros((K, 7), F)
+    for k in range(K):
+        ax = rng.standard_normal(3)
+        ax /= np.linalg.norm(ax)
+        ang = rng.uniform(ang_lo, ang_hi)
+        q = np.concatenate([np.sin(ang / 2) * ax, [np.cos(ang / 2)]])
+        if k % 3 == 1:
+            q = -q                                   # the same rotation with qw < 0
+        poses[k, :3] = rng.uniform(-tmax, tmax, 3)
+        poses[k, 3:] = q
+    return poses
+
+
+def _graph(rng, poses, disps, intr, radius):
+    K, h, w = disps.shape
+    ii, jj = _edges(K, radius)
+    N = len(ii)
+    weight = rng.uniform(0.0, 1.0, (N, 2, h, w)).astype(F)
+    noise = rng.normal(0.0, 0.5, (N, 2, h, w)).astype(F)
+    eta = (0.2 * rng.uniform(1e-3, 2e-2, (K, h, w)) + 1e-7).astype(F)
+    return dict(poses=poses, disps=disps, intrinsics=intr, ii=ii, jj=jj, weight=weight, noise=noise, eta=eta,
+                K=K, h=h, w=w)
+
+
+def general_graph(K, h, w, seed=7, radius=None):
+    """dict with the keys of synth.keyframe_graph; edges: all ordered pairs (radius=None) or |i - j| <= radius"""
+    rng = np.random.default_rng(seed)
+    poses = _random_poses(rng, K, 0.1, 0.5, 0.4)
+    y, x = np.meshgrid(np.arange(h, dtype=F), np.arange(w, dtype=F), indexing="ij")
+    disps = np.ones((K, h, w), F)
+    for k in range(K):
+        depth = 1.6 + 1.2 * np.sin(2 * np.pi * (x + 3 * k) / max(w, 2)) * np.cos(2 * np.pi * (y + 2 * k) / max(h, 2))
+        d = 1.0 / depth + rng.uniform(-0.01, 0.01, (h, w))
+        near = rng.uniform(0, 1, (h, w)) < 0.08
+        disps[k] = np.where(near, rng.uniform(2.0, 6.0, (h, w)), d).astype(F)
+    base = synth.camera(h, w)
+    intr = np.stack([base * (1 + rng.uniform(-0.1, 0.1, 4)) for _ in range(K)]).astype(F)
+    return _graph(rng, poses, disps, intr, radius)
+
+
+PLANES = ((np.array([0.1, -0.05, 1.0]), 2.0), (np.array([0.6, 0.0, 1.0]), 1.6))     # n . X = d in the world frame
+
+
+def plane_graph(K, h, w, seed=11, radius=None):
+    """multi-view consistent: every camera sees the nearest of two world planes (beyond 0.3), disparity noise +-0.4 %"""
+    rng = np.random.default_rng(seed)
+    poses = _random_poses(rng, K, 0.05, 0.25, 0.3)
+    row = (synth.camera(h, w) * np.array([1.07, 0.94, 1.03, 0.97], F)).astype(F)      # fx != fy
+    fx, fy, cx, cy = row.astype(np.float64)
+    y, x = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    disps = np.zeros((K, h, w), F)
+    for k in range(K):
+        c2w = np.linalg.inv(pose_matrix(poses[k]))
+        R, t = c2w[:3, :3], c2w[:3, 3]
+        ray = np.stack([(x - cx) / fx, (y - cy) / fy, np.ones_like(x)], -1) @ R.T
+        z = np.full((h, w), np.inf)
+        for n, d in PLANES:
+            with np.errstate(divide="ignore"):
+                zz = (d - n @ t) / (ray @ n)
+            z = np.minimum(z, np.where(zz > 0.3, zz, np.inf))
+        z = np.where(np.isfinite(z), z, 5.0)
+        disps[k] = (1.0 / z * (1 + rng.uniform(-0.004, 0.004, (h, w)))).astype(F)
+    intr = np.tile(row[None], (K, 1)).astype(F)
+    return _graph(rng, poses, disps, intr, radius)
+
+
+# ---- float64 reference ------------------------------------------------------------------------------------------------------
+def pose_matrix(pose):
+    """4 x 4 world -> camera matrix of [t | qx qy qz qw]; the rotation is scipy's (q and -q give the same matrix)"""
+    pose = np.asarray(pose, np.float64)
+    T = np.eye(4)
+    T[:3, :3] = Rotation.from_quat(pose[3:]).as_matrix()
+    T[:3, 3] = pose[:3]
+    return T
+
+
+STEREO = np.eye(4)
+STEREO[0, 3] = -0.1                                  # the fixed baseline of an ii == jj edge
+
+
+def relative_matrix(poses, i, j):
+    return pose_matrix(poses[j]) @ np.linalg.inv(pose_matrix(poses[i]))
+
+
+def _rays(h, w, intr, disp):
+    """homogeneous points [h,w,4] = (x - cx) / fx, (y - cy) / fy, 1, disparity"""
+    fx, fy, cx, cy = np.asarray(intr, np.float64)[:4]
+    y, x = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    return np.stack([(x - cx) / fx, (y - cy) / fy, np.ones_like(x), np.asarray(disp, np.float64)], -1), x, y
+
+
+def near(q, threshold):
+    """q within REL_BAND (relative) of `threshold`"""
+    return np.abs(np.asarray(q, np.float64) - threshold) <= REL_BAND * np.abs(threshold)
+
+
+def reproject64(poses, disps, intrinsics, ii, jj):
+    """-> coords [N,h,w,2] (Z < 0.1 replaced by 1 before the division), Z [N,h,w] of the transformed point; a point is valid
+    where Z > 0.2"""
+    _, h, w = disps.shape
+    coords = np.zeros((len(ii), h, w, 2))
+    Z = np.zeros((len(ii), h, w))
+    for n, (i, j) in enumerate(zip(ii, jj)):
+        i, j = int(i), int(j)
+        T = STEREO if i == j else relative_matrix(poses, i, j)
+        X0, _, _ = _rays(h, w, intrinsics[i], disps[i])
+        X1 = X0 @ T.T
+        fx, fy, cx, cy = np.asarray(intrinsics[j], np.float64)
+        Z[n] = X1[..., 2]
+        Zc = np.where(Z[n] < 0.1, 1.0, Z[n])
+        coords[n, ..., 0] = fx * X1[..., 0] / Zc + cx
+        coords[n, ..., 1] = fy * X1[..., 1] / Zc + cy
+    return coords, Z
+
+
+def frame_distance64(poses, disps, intrinsics, ii, jj, beta):
+    """-> dist [K] (1000 where the weighted share of valid terms V / T is below 0.75), V / T [K], and the depths
+    Z [K,2,h*w] of the two terms (full motion, translation only), valid where Z > 0.25"""
+    _, h, w = disps.shape
+    fx, fy, cx, cy = np.asarray(intrinsics, np.float64)[:4]
+    K = len(ii)
+    dist, ratio, Zs = np.zeros(K), np.zeros(K), np.zeros((K, 2, h * w))
+    wgt = np.array([beta, 1.0 - beta])[:, None]
+    for n, (i, j) in enumerate(zip(ii, jj)):
+        T = relative_matrix(poses, int(i), int(j))
+        X0, x, y = _rays(h, w, intrinsics, disps[int(i)])
+        Tt = np.eye(4)
+        Tt[:3, 3] = T[:3, 3]
+        d, ok = [], []
+        for M in (T, Tt):
+            X1 = X0 @ M.T
+            with np.errstate(divide="ignore", invalid="ignore"):
+                du = fx * X1[..., 0] / X1[..., 2] + cx - x
+                dv = fy * X1[..., 1] / X1[..., 2] + cy - y
+            d.append(np.hypot(du, dv).reshape(-1))
+            ok.append((X1[..., 2] > 0.25).reshape(-1))
+            Zs[n, len(d) - 1] = X1[..., 2].reshape(-1)
+        d, ok = np.array(d), np.array(ok)
+        V = (wgt * ok).sum()
+        ratio[n] = V / (h * w)
+        dist[n] = 1000.0 if ratio[n] < 0.75 else (wgt * np.where(ok, d, 0.0)).sum() / V
+    return dist, ratio, Zs
+
+
+def iproj64(poses, disps, intrinsics):
+    """-> points [num,h,w,3] = (T(pose) X)[:3] / disparity"""
+    num, h, w = disps.shape
+    pts = np.zeros((num, h, w, 3))
+    for b in range(num):
+        X0, _, _ = _rays(h, w, intrinsics, disps[b])
+        X1 = X0 @ pose_matrix(poses[b]).T
+        pts[b] = X1[..., :3] / X1[..., 3:4]
+    return pts
+
+
+def depth_filter64(poses, disps, intrinsics, ix, thresh):
+    """-> count [num,h,w] of the temporal neighbours ix-1..-3, ix+3..+5 that hold, at one of the 4 pixels around the
+    projection, a depth within thresh of the transformed point's; and edge [num,h,w], true where one of the depth
+    differences of that pixel lies within REL_BAND of thresh"""
+    B, h, w = disps.shape
+    fx, fy, cx, cy = np.asarray(intrinsics, np.float64)[:4]
+    D = np.asarray(disps, np.float64)
+    count = np.zeros((len(ix), h, w))
+    edge = np.zeros((len(ix), h, w), bool)
+    for b, i in enumerate(ix):
+        i = int(i)
+        X0, _, _ = _rays(h, w, intrinsics, disps[i])
+        for j in [i - 1, i - 2, i - 3, i + 3, i + 4, i + 5]:
+            if j < 0 or j >= B:
+                continue
+            X1 = X0 @ relative_matrix(poses, i, j).T
+            front = X1[..., 2] > 0
+            Z = np.where(front, X1[..., 2], 1.0)
+            u = fx * X1[..., 0] / Z + cx
+            v = fy * X1[..., 1] / Z + cy
+            u0, v0 = np.floor(u), np.floor(v)
+            inb = front & (u0 >= 0) & (v0 >= 0) & (u0 < w - 1) & (v0 < h - 1)
+            uc = np.clip(u0, 0, max(w - 2, 0)).astype(np.int64)
+            vc = np.clip(v0, 0, max(h - 2, 0)).astype(np.int64)
+            zj = Z / X1[..., 3]
+            hit = np.zeros((h, w), bool)
+            for oy, ox in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                diff = np.abs(zj - 1.0 / D[j][np.minimum(vc + oy, h - 1), np.minimum(uc + ox, w - 1)])
+                hit |= diff < thresh[b]
+                edge[b] |= inb & near(diff, float(thresh[b]))
+            count[b] += inb & hit
+    return count, edge

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+import geom_ref
 import glorie_slam_amd.synth as synth
 from oracle import ba as oba, geom as ogeom, se3
 
@@ -16,8 +17,12 @@ def _t(x, dev):
     return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
 
-def make_problem(K, h, w, radius=2, noise=0.5, perturb=True, seed=7, extra_edges=()):
-    g = synth.keyframe_graph(K=K, h=h, w=w, radius=radius, seed=seed, noise_px=noise)
+def make_problem(K, h, w, radius=2, noise=0.5, perturb=True, seed=7, extra_edges=(), graph=None):
+    """graph: a scene with the keys of synth.keyframe_graph to use instead of it (its edges; K, h, w, radius unused)"""
+    g = dict(graph) if graph is not None else \
+        synth.keyframe_graph(K=K, h=h, w=w, radius=radius, seed=seed, noise_px=noise)
+    g["poses"], g["disps"] = g["poses"].copy(), g["disps"].copy()
+    K, h, w = g["K"], g["h"], g["w"]
     ii = np.concatenate([g["ii"], [e[0] for e in extra_edges]]).astype(np.int64)
     jj = np.concatenate([g["jj"], [e[1] for e in extra_edges]]).astype(np.int64)
     rng = np.random.default_rng(seed)
@@ -53,6 +58,25 @@ def run_gpu(g, dev, t0, t1, iters, lm=1e-4, ep=0.1, motion_only=False, depth_onl
 def test_ba_matches_oracle(gpu, K, h, w, iters, radius):
     g = make_problem(K, h, w, radius=radius)
     t0, t1 = 1, K
+    rp, rd, rdx, rdz, info = oba.ba(g["poses"], g["disps"], g["intrinsics"][0], g["target"], g["weight"],
+                                    g["eta"], g["ii"], g["jj"], t0, t1, iters, 1e-4, 0.1)
+    assert info["failed"] == 0
+    p, d, dx, dz, st = run_gpu(g, gpu, t0, t1, iters)
+    assert st[0] == 0 and st[1] == K
+    np.testing.assert_allclose(dx, rdx, rtol=2e-3, atol=2e-6)
+    np.testing.assert_allclose(p, rp, atol=POSE_TOL)
+    np.testing.assert_allclose(d, rd, atol=DISP_TOL)
+    np.testing.assert_allclose(dz, rdz, rtol=5e-3, atol=2e-5)
+    assert np.array_equal(p[0], g["poses"][0])  # pose 0 is fixed (t0 = 1)
+
+
+@pytest.mark.parametrize("K,h,w", [(5, 12, 16), (6, 9, 13)])
+def test_ba_matches_oracle_on_general_poses(gpu, K, h, w):
+    """test_ba_matches_oracle where no quaternion component is zero (the synthetic graphs rotate about y only, which
+    multiplies every q.x / q.z term of se3_act, se3_adjT and the retraction by an exact zero) and fx != fy"""
+    g = make_problem(K, h, w, graph=geom_ref.plane_graph(K, h, w, radius=2))
+    assert np.all(g["poses"][:, 3:] != 0) and (g["poses"][:, 6] < 0).any()
+    t0, t1, iters = 1, K, 2
     rp, rd, rdx, rdz, info = oba.ba(g["poses"], g["disps"], g["intrinsics"][0], g["target"], g["weight"],
                                     g["eta"], g["ii"], g["jj"], t0, t1, iters, 1e-4, 0.1)
     assert info["failed"] == 0

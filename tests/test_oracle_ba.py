@@ -5,17 +5,28 @@ import numpy as np
 
 from oracle import ba as oba, geom as ogeom, se3
 import glorie_slam_amd.synth as synth
+import geom_ref
 
 
-def small_graph(K=4, h=12, w=16, noise=0.5, seed=5):
-    g = synth.keyframe_graph(K=K, h=h, w=w, radius=2, seed=seed, noise_px=noise)
+def small_graph(K=4, h=12, w=16, noise=0.5, seed=5, graph=None):
+    g = graph or synth.keyframe_graph(K=K, h=h, w=w, radius=2, seed=seed, noise_px=noise)
     coords, _ = ogeom.reproject(g["poses"], g["disps"], g["intrinsics"], g["ii"], g["jj"])
     g["target"] = (coords.transpose(0, 3, 1, 2) + g["noise"]).astype(np.float32)
     return g
 
 
 def test_jacobians_finite_difference():
-    g = small_graph()
+    check_jacobians(small_graph())
+
+
+def test_jacobians_finite_difference_general_poses():
+    """the same pin where no quaternion component is zero: rotations about random axes, fx != fy (geom_ref.plane_graph)"""
+    g = small_graph(graph=geom_ref.plane_graph(5, 12, 16, radius=2))
+    assert np.all(g["poses"][:, 3:] != 0)
+    check_jacobians(g)
+
+
+def check_jacobians(g):
     intr = g["intrinsics"][0]
     i, j = 1, 2
     n = [k for k in range(len(g["ii"])) if g["ii"][k] == i and g["jj"][k] == j][0]
