@@ -77,8 +77,8 @@ def general_graph(K, h, w, seed=7, radius=None):
 PLANES = ((np.array([0.1, -0.05, 1.0]), 2.0), (np.array([0.6, 0.0, 1.0]), 1.6))     # n . X = d in the world frame
 
 
-def plane_graph(K, h, w, seed=11, radius=None):
-    """multi-view consistent: every camera sees the nearest of two world planes (beyond 0.3), disparity noise +-0.4 %"""
+def plane_graph(K, h, w, seed=11, radius=None, planes=PLANES):
+    """multi-view consistent: every camera sees the nearest of the world planes (beyond 0.3), disparity noise +-0.4 %"""
     rng = np.random.default_rng(seed)
     poses = _random_poses(rng, K, 0.05, 0.25, 0.3)
     row = (synth.camera(h, w) * np.array([1.07, 0.94, 1.03, 0.97], F)).astype(F)      # fx != fy
@@ -90,7 +90,7 @@ def plane_graph(K, h, w, seed=11, radius=None):
         R, t = c2w[:3, :3], c2w[:3, 3]
         ray = np.stack([(x - cx) / fx, (y - cy) / fy, np.ones_like(x)], -1) @ R.T
         z = np.full((h, w), np.inf)
-        for n, d in PLANES:
+        for n, d in planes:
             with np.errstate(divide="ignore"):
                 zz = (d - n @ t) / (ray @ n)
             z = np.minimum(z, np.where(zz > 0.3, zz, np.inf))

@@ -48,9 +48,12 @@ def run_gpu(g, dev, itrs, edge_on=None, lm=1e-4, ep=0.1, eta=None):
     return disps.cpu().numpy(), sc.cpu().numpy(), sh.cpu().numpy(), ctx.ba_status()
 
 
-@pytest.mark.parametrize("itrs", [1, 2])
-def test_stage2_matches_dense_oracle(gpu, itrs):
-    g = problem()
+# K = 25 | 26: the last size solved inside the launch and the first that takes the separate solve launch
+@pytest.mark.parametrize("itrs,K", [pytest.param(1, 6, id="1"), pytest.param(2, 6, id="2"),
+                                    pytest.param(2, 25, id="2-K25"), pytest.param(2, 26, id="2-K26")])
+def test_stage2_matches_dense_oracle(gpu, itrs, K):
+    g = problem() if K == 6 else problem(K=K, h=7, w=9)
+    assert len(set(g["ii"].tolist())) == K
     d, s, q = g["disps"], g["scales"], g["shifts"]
     for _ in range(itrs):
         d, s, q, _ = odspo.ba_with_scale_shift(g["target"], g["weight_hw2"], g["eta"], g["poses"], d,
