@@ -14,16 +14,15 @@
 //   stores them once -- no zero-fill pass and no read-modify-write of the output as in the
 //   reference (4 RMW per output there).
 //
-// Numerics: for fp16 the reference's rounding sequence is reproduced exactly:
-//   out = ((((+0 + h(s00*w00)) + h(s01*w01)) + h(s10*w10)) + h(s11*w11)), every product and
-//   every sum rounded to fp16 (c10::Half operators), w** = h(float weight).  Out-of-bounds
-//   samples are skipped in the reference; adding +0 instead is bit-identical because the
-//   accumulator can never be -0.  fp contraction is disabled in that block.
+// Numerics: for fp16 the reference's rounding sequence is reproduced exactly (blend4 and
+//   weight_cast of corr_common.hiph).  Out-of-bounds samples are skipped in the reference;
+//   adding +0 instead is bit-identical because the accumulator can never be -0.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include "../../include/glorie_hip.h"
 #include "common.hiph"
+#include "corr_common.hiph"
 
 namespace glorie {
 
@@ -39,38 +38,6 @@ template <typename T> struct Row8;
 template <> struct __attribute__((packed, aligned(2))) Row8<_Float16> { _Float16 v[8]; };
 template <> struct __attribute__((packed, aligned(4))) Row8<float> { float v[8]; };
 
-// bilinear blend of the 2x2 neighbourhood in the reference's accumulation order
-__device__ __forceinline__ _Float16 blend4(_Float16 s00, _Float16 s01, _Float16 s10, _Float16 s11,
-                                           _Float16 w00, _Float16 w01, _Float16 w10, _Float16 w11) {
-#pragma clang fp contract(off)
-  _Float16 acc = (_Float16)0.0f;
-  _Float16 t;
-  t = s00 * w00; acc = acc + t;
-  t = s01 * w01; acc = acc + t;
-  t = s10 * w10; acc = acc + t;
-  t = s11 * w11; acc = acc + t;
-  return acc;
-}
-// fp32: nvcc contracts `corr += s * w` into an FMA chain in the reference build
-__device__ __forceinline__ float blend4(float s00, float s01, float s10, float s11,
-                                        float w00, float w01, float w10, float w11) {
-  float acc = 0.0f;
-  acc = fmaf(s00, w00, acc);
-  acc = fmaf(s01, w01, acc);
-  acc = fmaf(s10, w10, acc);
-  acc = fmaf(s11, w11, acc);
-  return acc;
-}
-
-// float -> T weight.  The reference rounds the fp32 product to fp32 FIRST and then to fp16
-// (`scalar_t(dx * dy)`); hipcc would otherwise fuse mul+cvt into v_fma_mixlo_f16 (a single
-// rounding), which differs in rare near-tie cases.  The empty asm pins the fp32 value.
-template <typename T>
-__device__ __forceinline__ T weight_cast(float prod) {
-  asm volatile("" : "+v"(prod));
-  return (T)prod;
-}
-
 __device__ __forceinline__ _Float16 shfl_next(_Float16 v) {
   // move one fp16 from lane+1; done on the 32-bit container
   int x = (int)__builtin_bit_cast(unsigned short, v);
@@ -85,7 +52,7 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_kernel(
     CorrLevels lv, int num_levels, int scale_coords,
     const float* __restrict__ coords, T* __restrict__ out,
     int HW, int out_channels) {
-  constexpr int R = 3, RD = 7, WIN = 8;
+  constexpr int RD = 7, WIN = 8;
   const int tid = threadIdx.x;
   const int row = tid & 7;
   const int p = blockIdx.x * 32 + (tid >> 3);
@@ -102,10 +69,8 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_kernel(
     const float xs = scale_coords ? x0 * inv : x0;
     const float ys = scale_coords ? y0 * inv : y0;
     inv *= 0.5f;
-    const float fx = floorf(xs), fy = floorf(ys);
-    const float dx = xs - fx, dy = ys - fy;
-    const int ix0 = static_cast<int>(fx) - R;
-    const int y1 = static_cast<int>(fy) - R + row;
+    const CorrWindow win = corr_window(xs, ys);
+    const int ix0 = win.ix0, y1 = win.iy0 + row;
 
     T s[WIN];
 #pragma unroll
@@ -131,16 +96,12 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_kernel(
 #pragma unroll
     for (int i = 0; i < WIN; ++i) nx[i] = shfl_next(s[i]);
 
-    const T w00 = weight_cast<T>((1.0f - dx) * (1.0f - dy));
-    const T w01 = weight_cast<T>((1.0f - dx) * dy);
-    const T w10 = weight_cast<T>(dx * (1.0f - dy));
-    const T w11 = weight_cast<T>(dx * dy);
-
+    const CorrWeights<T> wt = corr_weights<T>(win.dx, win.dy);
     if (live && row < RD) {
       T* o = out + ((size_t)n * out_channels + (size_t)l * RD * RD + row) * HW + p;
 #pragma unroll
       for (int i = 0; i < RD; ++i) {
-        const T v = blend4(s[i], nx[i], s[i + 1], nx[i + 1], w00, w01, w10, w11);
+        const T v = blend4(s[i], nx[i], s[i + 1], nx[i + 1], wt);
         o[(size_t)i * RD * HW] = v;
       }
     }
@@ -156,22 +117,14 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_kernel(
 // instructions, 1.8x write amplification in WRITE_SIZE).  Row r+1 comes from lane+1 via a DPP
 // row shift.  Requires HW % 8 == 0.  Arithmetic identical to v1 (bit-exact fp16).
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned dpp_next(unsigned v) {
-  // lane i <- lane i+1 inside a row of 16 lanes (row_shl:1); the last row lane is unused
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true);
-}
-
 template <typename T> struct Pack8;
 template <> struct Pack8<_Float16> {
-  typedef __attribute__((ext_vector_type(4))) unsigned vec;  // 8 halfs
   static __device__ __forceinline__ void next(const _Float16 (&s)[8], _Float16 (&n)[8]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const unsigned lo = __builtin_bit_cast(unsigned short, s[2 * i]);
-      const unsigned hi = __builtin_bit_cast(unsigned short, s[2 * i + 1]);
-      const unsigned v = dpp_next(lo | (hi << 16));
-      n[2 * i] = __builtin_bit_cast(_Float16, (unsigned short)(v & 0xffffu));
-      n[2 * i + 1] = __builtin_bit_cast(_Float16, (unsigned short)(v >> 16));
+      const unsigned v = dpp_next(h_pack(s[2 * i], s[2 * i + 1]));
+      n[2 * i] = h_lo(v);
+      n[2 * i + 1] = h_hi(v);
     }
   }
 };
@@ -185,11 +138,38 @@ template <> struct Pack8<float> {
 template <typename T>
 struct __attribute__((aligned(16))) Out8 { T v[8]; };
 
+// coordinates of the 8 consecutive pixels p .. p + 7 of edge n: planar [N][2][HW], or interleaved [N][HW][2] as the
+// reprojection writes it (no permute + copy in front of the lookup: 8 pixels = 64 contiguous bytes)
+__device__ __forceinline__ void load_coords8(const float* coords, int n, int HW, int p, bool interleaved, float (&x)[8],
+                                             float (&y)[8]) {
+  if (interleaved) {
+    const float4* cp = reinterpret_cast<const float4*>(coords + ((size_t)n * HW + p) * 2);
+    const float4 a = cp[0], b = cp[1], c = cp[2], d = cp[3];
+    x[0] = a.x; y[0] = a.y; x[1] = a.z; y[1] = a.w; x[2] = b.x; y[2] = b.y; x[3] = b.z; y[3] = b.w;
+    x[4] = c.x; y[4] = c.y; x[5] = c.z; y[5] = c.w; x[6] = d.x; y[6] = d.y; x[7] = d.z; y[7] = d.w;
+  } else {
+    const float4* cx = reinterpret_cast<const float4*>(coords + ((size_t)n * 2 + 0) * HW + p);
+    const float4* cy = reinterpret_cast<const float4*>(coords + ((size_t)n * 2 + 1) * HW + p);
+    const float4 a = cx[0], b = cx[1], c = cy[0], d = cy[1];
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+    y[0] = c.x; y[1] = c.y; y[2] = c.z; y[3] = c.w; y[4] = d.x; y[5] = d.y; y[6] = d.z; y[7] = d.w;
+  }
+}
+// planar output [N][channels][HW]: window row `row` of level l, taps i = 0..6 of the 8 pixels pb .. pb + 7 - one 16-byte
+// store per channel l * 49 + i * 7 + row
+template <typename T>
+__device__ __forceinline__ void store_planar8(T* out, int n, int out_channels, int l, int row, int HW, int pb,
+                                              const Out8<T> (&o)[7]) {
+  T* op = out + ((size_t)n * out_channels + (size_t)l * 49 + row) * HW + pb;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) *reinterpret_cast<Out8<T>*>(op + (size_t)i * 7 * HW) = o[i];
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void corr_lookup_r3_v2_kernel(
     CorrLevels lv, int num_levels, int scale_coords, const float* __restrict__ coords,
     T* __restrict__ out, int HW, int out_channels) {
-  constexpr int R = 3, RD = 7, WIN = 8, PG = 8;
+  constexpr int RD = 7, WIN = 8, PG = 8;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int row = lane & 7, grp = lane >> 3;
   const int n = blockIdx.y;
@@ -198,13 +178,7 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_v2_kernel(
   const int pc = live ? pb : HW - PG;
 
   float x0[PG], y0[PG];
-  {
-    const float4* cx = reinterpret_cast<const float4*>(coords + ((size_t)n * 2 + 0) * HW + pc);
-    const float4* cy = reinterpret_cast<const float4*>(coords + ((size_t)n * 2 + 1) * HW + pc);
-    const float4 a = cx[0], b = cx[1], c = cy[0], d = cy[1];
-    x0[0] = a.x; x0[1] = a.y; x0[2] = a.z; x0[3] = a.w; x0[4] = b.x; x0[5] = b.y; x0[6] = b.z; x0[7] = b.w;
-    y0[0] = c.x; y0[1] = c.y; y0[2] = c.z; y0[3] = c.w; y0[4] = d.x; y0[5] = d.y; y0[6] = d.z; y0[7] = d.w;
-  }
+  load_coords8(coords, n, HW, pc, false, x0, y0);
   float inv = 1.0f;
   for (int l = 0; l < num_levels; ++l) {
     const int h2 = lv.h2[l], w2 = lv.w2[l];
@@ -216,11 +190,10 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_v2_kernel(
     for (int q = 0; q < PG; ++q) {
       const float xs = scale_coords ? x0[q] * inv : x0[q];
       const float ys = scale_coords ? y0[q] * inv : y0[q];
-      const float fx = floorf(xs), fy = floorf(ys);
-      dxs[q] = xs - fx;
-      dys[q] = ys - fy;
-      const int ix0 = static_cast<int>(fx) - R;
-      const int y1 = static_cast<int>(fy) - R + row;
+      const CorrWindow win = corr_window(xs, ys);
+      dxs[q] = win.dx;
+      dys[q] = win.dy;
+      const int ix0 = win.ix0, y1 = win.iy0 + row;
 #pragma unroll
       for (int i = 0; i < WIN; ++i) s[q][i] = (T)0.0f;
       if (y1 >= 0 && y1 < h2) {
@@ -246,21 +219,12 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_v2_kernel(
     for (int q = 0; q < PG; ++q) {
       T nx[WIN];
       Pack8<T>::next(s[q], nx);
-      const float dx = dxs[q], dy = dys[q];
-      const T w00 = weight_cast<T>((1.0f - dx) * (1.0f - dy));
-      const T w01 = weight_cast<T>((1.0f - dx) * dy);
-      const T w10 = weight_cast<T>(dx * (1.0f - dy));
-      const T w11 = weight_cast<T>(dx * dy);
+      const CorrWeights<T> wt = corr_weights<T>(dxs[q], dys[q]);
 #pragma unroll
       for (int i = 0; i < RD; ++i)
-        o[i].v[q] = blend4(s[q][i], nx[i], s[q][i + 1], nx[i + 1], w00, w01, w10, w11);
+        o[i].v[q] = blend4(s[q][i], nx[i], s[q][i + 1], nx[i + 1], wt);
     }
-    if (live && row < RD) {
-      T* op = out + ((size_t)n * out_channels + (size_t)l * RD * RD + row) * HW + pb;
-#pragma unroll
-      for (int i = 0; i < RD; ++i)
-        *reinterpret_cast<Out8<T>*>(op + (size_t)i * RD * HW) = o[i];
-    }
+    if (live && row < RD) store_planar8(out, n, out_channels, l, row, HW, pb, o);
   }
 }
 
@@ -276,8 +240,6 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_v2_kernel(
 // Arithmetic identical to v1/v2 (bit-exact fp16).  The volume needs 16 bytes of readable slack on
 // either side (a plane is >= 256 bytes: the Python side allocates one spare plane before and after).
 // ------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-
 // CL: the output is channels-last with the window padded to 8 x 8 per level - channel l * 64 + row * 8 + tap, rows / taps 7
 // zero - i.e. one 512-byte row of 256 halfs per pixel.  The lane that owns window row `row` of a pixel then writes ONE 16-byte
 // piece (its 7 taps + a zero), the 8 row lanes of a pixel group together one full 128-byte line per (pixel, level): the same
@@ -288,7 +250,7 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_tiled_kernel(
     CorrLevels lv, int num_levels, const float* __restrict__ coords, _Float16* __restrict__ out,
     int HW, int out_channels, const int* __restrict__ slots, int coords_xy) {
   typedef _Float16 T;
-  constexpr int R = 3, RD = 7, WIN = 8, PG = 8;
+  constexpr int RD = 7, WIN = 8, PG = 8;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int row = lane & 7, grp = lane >> 3;
   const int n = blockIdx.y;
@@ -299,19 +261,7 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_tiled_kernel(
   const int pc = live ? pb : HW - PG;
 
   float x0[PG], y0[PG];
-  if (coords_xy) {
-    // [N][HW][2] as the reprojection writes it (no permute + copy in front of the lookup): 8 pixels = 64 contiguous bytes
-    const float4* cp = reinterpret_cast<const float4*>(coords + ((size_t)n * HW + pc) * 2);
-    const float4 a = cp[0], b = cp[1], c = cp[2], d = cp[3];
-    x0[0] = a.x; y0[0] = a.y; x0[1] = a.z; y0[1] = a.w; x0[2] = b.x; y0[2] = b.y; x0[3] = b.z; y0[3] = b.w;
-    x0[4] = c.x; y0[4] = c.y; x0[5] = c.z; y0[5] = c.w; x0[6] = d.x; y0[6] = d.y; x0[7] = d.z; y0[7] = d.w;
-  } else {
-    const float4* cx = reinterpret_cast<const float4*>(coords + ((size_t)n * 2 + 0) * HW + pc);
-    const float4* cy = reinterpret_cast<const float4*>(coords + ((size_t)n * 2 + 1) * HW + pc);
-    const float4 a = cx[0], b = cx[1], c = cy[0], d = cy[1];
-    x0[0] = a.x; x0[1] = a.y; x0[2] = a.z; x0[3] = a.w; x0[4] = b.x; x0[5] = b.y; x0[6] = b.z; x0[7] = b.w;
-    y0[0] = c.x; y0[1] = c.y; y0[2] = c.z; y0[3] = c.w; y0[4] = d.x; y0[5] = d.y; y0[6] = d.z; y0[7] = d.w;
-  }
+  load_coords8(coords, n, HW, pc, coords_xy != 0, x0, y0);
   float inv = 1.0f;
   for (int l = 0; l < num_levels; ++l) {
     const int h2 = lv.h2[l], w2 = lv.w2[l];
@@ -324,12 +274,10 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_tiled_kernel(
     // phase 1: issue the 16 loads of this lane (2 per pixel of the group)
 #pragma unroll
     for (int q = 0; q < PG; ++q) {
-      const float xs = x0[q] * inv, ys = y0[q] * inv;
-      const float fx = floorf(xs), fy = floorf(ys);
-      dxs[q] = xs - fx;
-      dys[q] = ys - fy;
-      const int ix0 = static_cast<int>(fx) - R;
-      const int y1 = static_cast<int>(fy) - R + row;
+      const CorrWindow win = corr_window(x0[q] * inv, y0[q] * inv);
+      dxs[q] = win.dx;
+      dys[q] = win.dy;
+      const int ix0 = win.ix0, y1 = win.iy0 + row;
       const bool yok = y1 >= 0 && y1 < h2;
       const int bx0 = ix0 >> 3, sh = ix0 & 7;               // floor division / modulo for negative starts too
       const bool va = yok && bx0 >= 0 && bx0 < nbx;
@@ -360,14 +308,10 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_tiled_kernel(
       __builtin_memcpy(sq, &sv, 16);
       T nx[WIN];
       Pack8<T>::next(sq, nx);
-      const float dx = dxs[q], dy = dys[q];
-      const T w00 = weight_cast<T>((1.0f - dx) * (1.0f - dy));
-      const T w01 = weight_cast<T>((1.0f - dx) * dy);
-      const T w10 = weight_cast<T>(dx * (1.0f - dy));
-      const T w11 = weight_cast<T>(dx * dy);
+      const CorrWeights<T> wt = corr_weights<T>(dxs[q], dys[q]);
 #pragma unroll
       for (int i = 0; i < RD; ++i)
-        o[i].v[q] = blend4(sq[i], nx[i], sq[i + 1], nx[i + 1], w00, w01, w10, w11);
+        o[i].v[q] = blend4(sq[i], nx[i], sq[i + 1], nx[i + 1], wt);
     }
     if (CL) {
       if (live) {
@@ -382,10 +326,7 @@ __global__ __launch_bounds__(256) void corr_lookup_r3_tiled_kernel(
         }
       }
     } else if (live && row < RD) {
-      T* op = out + ((size_t)n * out_channels + (size_t)l * RD * RD + row) * HW + pb;
-#pragma unroll
-      for (int i = 0; i < RD; ++i)
-        *reinterpret_cast<Out8<T>*>(op + (size_t)i * RD * HW) = o[i];
+      store_planar8(out, n, out_channels, l, row, HW, pb, o);
     }
   }
 }
@@ -407,23 +348,17 @@ __global__ __launch_bounds__(256) void corr_lookup_generic_kernel(
     const float xs = scale_coords ? x0 * inv : x0;
     const float ys = scale_coords ? y0 * inv : y0;
     inv *= 0.5f;
-    const float fx = floorf(xs), fy = floorf(ys);
-    const float dx = xs - fx, dy = ys - fy;
-    const int ix0 = static_cast<int>(fx) - radius;
-    const int iy0 = static_cast<int>(fy) - radius;
+    const CorrWindow win = corr_window(xs, ys, radius);
+    const int ix0 = win.ix0, iy0 = win.iy0;
     const T* plane = reinterpret_cast<const T*>(lv.vol[l]) + ((size_t)n * HW + p) * ((size_t)h2 * w2);
-    const T w00 = weight_cast<T>((1.0f - dx) * (1.0f - dy));
-    const T w01 = weight_cast<T>((1.0f - dx) * dy);
-    const T w10 = weight_cast<T>(dx * (1.0f - dy));
-    const T w11 = weight_cast<T>(dx * dy);
+    const CorrWeights<T> wt = corr_weights<T>(win.dx, win.dy);
     auto fetch = [&](int i, int j) -> T {
       const int x1 = ix0 + i, y1 = iy0 + j;
       return (x1 >= 0 && x1 < w2 && y1 >= 0 && y1 < h2) ? plane[(size_t)y1 * w2 + x1] : (T)0.0f;
     };
     for (int i = 0; i < rd; ++i)
       for (int j = 0; j < rd; ++j) {
-        const T v = blend4(fetch(i, j), fetch(i, j + 1), fetch(i + 1, j), fetch(i + 1, j + 1),
-                           w00, w01, w10, w11);
+        const T v = blend4(fetch(i, j), fetch(i, j + 1), fetch(i + 1, j), fetch(i + 1, j + 1), wt);
         out[((size_t)n * out_channels + (size_t)l * rd * rd + (size_t)i * rd + j) * HW + p] = v;
       }
   }

@@ -25,7 +25,7 @@
 // instead of 256 gathers, +12 % bytes for windows that start on an odd column): wherever the flow is locally constant all
 // 64 lanes hit ONE line, and the union over the 8 x 8 window is ~(8 + spread)^2 / 2 lines per 64 pixels instead of 64 x 3.5.
 // Same footprint (planes are padded to whole tiles: +6.7 % at 60 x 80), same values, so the arithmetic of the lookup
-// (c10::Half products and sums, see corr.hip) is reproduced bit for bit.
+// (c10::Half products and sums, corr_common.hiph) is reproduced bit for bit.
 //
 // The lookup keeps a pixel's 4 x 7 x 7 outputs in its lane, so corr_encoder[0] runs as an MFMA epilogue in the same launch
 // (out^T[128 ch x 64 px] = W[128 x 224] corr^T, K ordered l*56 + j*8 + i, tap 7 of every row zero): the lane's packed
@@ -36,15 +36,12 @@
 #include <stdint.h>
 #include <algorithm>
 #include <stdlib.h>
-#include "common.hiph"
+#include "corr_pyramid.hiph"
 
 namespace glorie {
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 struct DmArgs {
   const _Float16* lvl[4];     // arena levels [capacity][ntiles][(h>>l) * Wp][64], Wp = even(w>>l)
@@ -64,13 +61,6 @@ struct DmArgs {
 constexpr unsigned kOobStore = 0xc0000000u;   // same for the encoder's output rows (one launch covers less than 2 GB of them)
 constexpr unsigned kOob = 0x40000000u;   // byte offset far beyond any plane: the buffer load returns 0 without a memory access
 
-__device__ __forceinline__ _Float16 to_half_rn(float prod) {
-  // the reference rounds the fp32 weight product to fp32 first and then to fp16 (`scalar_t(dx * dy)`); the empty asm keeps hipcc
-  // from fusing mul + cvt into one v_fma_mixlo_f16 (single rounding, differs in rare near-ties) - same as corr.hip
-  asm volatile("" : "+v"(prod));
-  return (_Float16)prod;
-}
-__device__ __forceinline__ h2 splat(_Float16 v) { return h2{v, v}; }
 // Window columns i = 0..7 of a lane start at displaced column bx; the five dwords D[0..4] of a window row hold the displaced
 // columns e .. e + 9, e = bx - (bx & 1).  A packed pair of taps is ONE v_perm_b32 of two neighbouring dwords with a per-lane
 // selector (perm(D[k+1], D[k], sel): selector bytes 0-3 name D[k], 4-7 D[k+1], 0x0c yields zero):
@@ -91,7 +81,8 @@ __device__ __forceinline__ h2 perm2(unsigned d1, unsigned d0, unsigned sel) {
   return __builtin_bit_cast(h2, __builtin_amdgcn_perm(d1, d0, sel));
 }
 
-// one term of the reference's accumulation: products and sums individually rounded to fp16 (no contraction)
+// one term of the reference's accumulation: products and sums individually rounded to fp16 (no contraction) - blend4's
+// rounding contract on a packed pair of taps
 __device__ __forceinline__ h2 acc_term(h2 acc, h2 s, h2 w) {
 #pragma clang fp contract(off)
   const h2 t = s * w;
@@ -108,11 +99,10 @@ __device__ __forceinline__ void dm_gather(const DmArgs& a, size_t slot_tile, int
                                           unsigned (&raw)[8][5], unsigned (&selp)[4], unsigned (&selq)[4], float& fdx, float& fdy) {
   const int hl = a.h >> L, wl = a.w >> L, wp = (wl + 1) & ~1;
   const float inv = 1.0f / (float)(1 << L);
-  const float xs = x0 * inv, ys = y0 * inv;
-  const float fx = floorf(xs), fy = floorf(ys);
-  fdx = xs - fx;
-  fdy = ys - fy;
-  const int ix0 = static_cast<int>(fx) - 3, iy0 = static_cast<int>(fy) - 3;
+  const CorrWindow win = corr_window(x0 * inv, y0 * inv);
+  fdx = win.dx;
+  fdy = win.dy;
+  const int ix0 = win.ix0, iy0 = win.iy0;
   int bx = ix0 - (sx >> L) + (wl >> 1);
   bx %= wp;
   bx = bx < 0 ? bx + wp : bx;
@@ -150,10 +140,7 @@ __device__ __forceinline__ void dm_gather(const DmArgs& a, size_t slot_tile, int
 // contributions reach corr[i][j] in exactly this order), evaluated for taps (2k, 2k+1) at once on the packed fp16 pipes
 __device__ __forceinline__ void dm_blend(const unsigned (&raw)[8][5], float fdx, float fdy, const unsigned (&selp)[4],
                                          const unsigned (&selq)[4], u32x4 (&rows)[7]) {
-  const h2 w00 = splat(to_half_rn((1.0f - fdx) * (1.0f - fdy)));
-  const h2 w01 = splat(to_half_rn((1.0f - fdx) * fdy));
-  const h2 w10 = splat(to_half_rn(fdx * (1.0f - fdy)));
-  const h2 w11 = splat(to_half_rn(fdx * fdy));
+  const CorrWeights<h2> wt = corr_weights<h2>(fdx, fdy);          // every weight in both halves of its pair
   h2 P[2][4], Q[2][4];            // window rows j, j + 1: pairs (2k, 2k+1) and (2k+1, 2k+2)
   auto pack_row = [&](int j, h2 (&p)[4], h2 (&q)[4]) {
 #pragma unroll
@@ -173,10 +160,10 @@ __device__ __forceinline__ void dm_blend(const unsigned (&raw)[8][5], float fdx,
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       h2 acc = h2{(_Float16)0.0f, (_Float16)0.0f};
-      acc = acc_term(acc, p0[k], w00);
-      acc = acc_term(acc, p1[k], w01);
-      acc = acc_term(acc, q0[k], w10);
-      acc = acc_term(acc, q1[k], w11);
+      acc = acc_term(acc, p0[k], wt.w00);
+      acc = acc_term(acc, p1[k], wt.w01);
+      acc = acc_term(acc, q0[k], wt.w10);
+      acc = acc_term(acc, q1[k], wt.w11);
       unsigned u = __builtin_bit_cast(unsigned, acc);
       if (k == 3) u &= 0xffffu;           // tap 7 is padding
       rows[j][k] = u;
@@ -200,35 +187,51 @@ __device__ __forceinline__ void dm_level(const DmArgs& a, size_t slot_tile, int 
   }
 }
 
+// a work unit = (edge n, tile): the pipelined kernel keeps only the wave-uniform part across its stages, the lane's pixel is
+// recomputed
+struct DmUnit { int n, tile, slot_tile; };
+struct DmPixel { int sy, sx, pix; bool live; };
+__device__ __forceinline__ void dm_unit(const DmArgs& a, int unit, DmUnit& u) {
+  const int ntiles = a.ntx * a.nty;
+  u.n = unit / ntiles;
+  u.tile = unit - u.n * ntiles;
+  const int slot = a.slots ? a.slots[u.n] : a.slot0 + u.n;
+  u.slot_tile = __builtin_amdgcn_readfirstlane(slot * ntiles + u.tile);
+}
+__device__ __forceinline__ DmPixel dm_pixel(const DmArgs& a, const DmUnit& u, int lane) {
+  DmPixel p;
+  const int ty = u.tile / a.ntx, tx = u.tile - ty * a.ntx;
+  p.sy = ty * 8 + (lane >> 3);
+  p.sx = tx * 8 + (lane & 7);
+  p.live = p.sy < a.h && p.sx < a.w;
+  p.pix = min(p.sy, a.h - 1) * a.w + min(p.sx, a.w - 1);
+  return p;
+}
+__device__ __forceinline__ float2 dm_coords(const DmArgs& a, const DmUnit& u, const DmPixel& p, bool on) {
+  const int HW = a.h * a.w;
+  float2 c;
+  if (a.coords_xy) c = *reinterpret_cast<const float2*>(a.coords + ((size_t)u.n * HW + p.pix) * 2);
+  else c = make_float2(a.coords[((size_t)u.n * 2 + 0) * HW + p.pix], a.coords[((size_t)u.n * 2 + 1) * HW + p.pix]);
+  if (!(on && p.live)) { c.x = -1.0e6f; c.y = -1.0e6f; }          // padding lanes: every tap out of range, no memory access
+  return c;
+}
+
 // plain lookup (channels-last 256-channel result): grid (ceil(ntiles / 4), N); 256 threads = 4 waves = 4 consecutive tiles
 __global__ __launch_bounds__(256) void corr_dm_lookup_kernel(DmArgs a) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ntiles = a.ntx * a.nty;
-  const int n = blockIdx.y;
   const int tile = blockIdx.x * 4 + wv;
   if (tile >= ntiles) return;
-  const int ty = tile / a.ntx, tx = tile - ty * a.ntx;
-  const int sy = ty * 8 + (lane >> 3), sx = tx * 8 + (lane & 7);
-  const bool live = sy < a.h && sx < a.w;
-  const int HW = a.h * a.w;
-  const int p = min(sy, a.h - 1) * a.w + min(sx, a.w - 1);
-  float x0, y0;
-  if (a.coords_xy) {
-    const float2 c = *reinterpret_cast<const float2*>(a.coords + ((size_t)n * HW + p) * 2);
-    x0 = c.x; y0 = c.y;
-  } else {
-    x0 = a.coords[((size_t)n * 2 + 0) * HW + p];
-    y0 = a.coords[((size_t)n * 2 + 1) * HW + p];
-  }
-  if (!live) { x0 = -1.0e6f; y0 = -1.0e6f; }          // padding lanes: every tap out of range, no memory access
-  const size_t slot = a.slots ? (size_t)a.slots[n] : (size_t)n;
-  const size_t slot_tile = slot * (size_t)ntiles + (size_t)tile;
-  const size_t row = (size_t)n * HW + p;
-  dm_level<0>(a, slot_tile, sy, sx, lane, x0, y0, live, row);
-  dm_level<1>(a, slot_tile, sy, sx, lane, x0, y0, live, row);
-  dm_level<2>(a, slot_tile, sy, sx, lane, x0, y0, live, row);
-  dm_level<3>(a, slot_tile, sy, sx, lane, x0, y0, live, row);
+  DmUnit u;
+  dm_unit(a, blockIdx.y * ntiles + tile, u);
+  const DmPixel px = dm_pixel(a, u, lane);
+  const float2 c = dm_coords(a, u, px, true);
+  const size_t slot_tile = (size_t)u.slot_tile, row = (size_t)u.n * (a.h * a.w) + px.pix;
+  dm_level<0>(a, slot_tile, px.sy, px.sx, lane, c.x, c.y, px.live, row);
+  dm_level<1>(a, slot_tile, px.sy, px.sx, lane, c.x, c.y, px.live, row);
+  dm_level<2>(a, slot_tile, px.sy, px.sx, lane, c.x, c.y, px.live, row);
+  dm_level<3>(a, slot_tile, px.sy, px.sx, lane, c.x, c.y, px.live, row);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -253,7 +256,7 @@ struct DmLevel {
   unsigned selp[4], selq[4];
   unsigned r, uy;                 // running: byte offset of the next window row (+ the lane's dword), its target row as unsigned
   unsigned rstep, rend, lane4, hl;
-  h2 w00, w01, w10, w11;
+  CorrWeights<h2> w;              // every weight in both halves: taps are blended in packed pairs
 };
 
 template <int L>
@@ -261,10 +264,8 @@ __device__ __forceinline__ void dm_setup(const DmArgs& a, size_t slot_tile, int 
                                          DmLevel& st) {
   const int hl = a.h >> L, wl = a.w >> L, wp = (wl + 1) & ~1, wp2 = wp >> 1;
   const float inv = 1.0f / (float)(1 << L);
-  const float xs = x0 * inv, ys = y0 * inv;
-  const float fx = floorf(xs), fy = floorf(ys);
-  const float fdx = xs - fx, fdy = ys - fy;
-  const int ix0 = static_cast<int>(fx) - 3, iy0 = static_cast<int>(fy) - 3;
+  const CorrWindow win = corr_window(x0 * inv, y0 * inv);
+  const int ix0 = win.ix0, iy0 = win.iy0;
   // |displacement| < 2 planes for every coordinate that has a valid tap at all; others only need SOME in-range value
   int bx = ix0 - (sx >> L) + (wl >> 1), by = iy0 - (sy >> L) + (hl >> 1);
   bx = bx < 0 ? bx + wp : (bx >= wp ? bx - wp : bx);
@@ -291,10 +292,7 @@ __device__ __forceinline__ void dm_setup(const DmArgs& a, size_t slot_tile, int 
   st.r = (unsigned)by * cend + st.lane4;
   st.uy = (unsigned)iy0;
   st.hl = (unsigned)hl;
-  st.w00 = splat(to_half_rn((1.0f - fdx) * (1.0f - fdy)));
-  st.w01 = splat(to_half_rn((1.0f - fdx) * fdy));
-  st.w10 = splat(to_half_rn(fdx * (1.0f - fdy)));
-  st.w11 = splat(to_half_rn(fdx * fdy));
+  st.w = corr_weights<h2>(win.dx, win.dy);
 }
 
 // the next window row (rows are requested in order, 0..7): five dwords = ten displaced columns
@@ -330,11 +328,11 @@ __device__ __forceinline__ u32x4 dm_blend_row(const DmLevel& st, const h2 (&p0)[
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     h2 acc;
-    if (EXACT) acc = acc_term(h2{(_Float16)0.0f, (_Float16)0.0f}, p0[k], st.w00);
-    else acc = acc_term0(p0[k], st.w00);
-    acc = acc_term(acc, p1[k], st.w01);
-    acc = acc_term(acc, q0[k], st.w10);
-    acc = acc_term(acc, q1[k], st.w11);
+    if (EXACT) acc = acc_term(h2{(_Float16)0.0f, (_Float16)0.0f}, p0[k], st.w.w00);
+    else acc = acc_term0(p0[k], st.w.w00);
+    acc = acc_term(acc, p1[k], st.w.w01);
+    acc = acc_term(acc, q0[k], st.w.w10);
+    acc = acc_term(acc, q1[k], st.w.w11);
     unsigned u = __builtin_bit_cast(unsigned, acc);
     if (EXACT && k == 3) u &= 0xffffu;
     r[k] = u;
@@ -389,34 +387,6 @@ __device__ __forceinline__ void dm_level_pipelined(const DmArgs& a, bool live, s
 #endif
   }
   if (CORR && live) *reinterpret_cast<u32x4*>(a.corr_cl + row * 256 + L * 64 + 56) = u32x4{0u, 0u, 0u, 0u};
-}
-
-// a work unit = (edge n, tile): only the wave-uniform part is kept across the pipeline, the lane's pixel is recomputed
-struct DmUnit { int n, tile, slot_tile; };
-struct DmPixel { int sy, sx, pix; bool live; };
-__device__ __forceinline__ void dm_unit(const DmArgs& a, int unit, DmUnit& u) {
-  const int ntiles = a.ntx * a.nty;
-  u.n = unit / ntiles;
-  u.tile = unit - u.n * ntiles;
-  const int slot = a.slots ? a.slots[u.n] : a.slot0 + u.n;
-  u.slot_tile = __builtin_amdgcn_readfirstlane(slot * ntiles + u.tile);
-}
-__device__ __forceinline__ DmPixel dm_pixel(const DmArgs& a, const DmUnit& u, int lane) {
-  DmPixel p;
-  const int ty = u.tile / a.ntx, tx = u.tile - ty * a.ntx;
-  p.sy = ty * 8 + (lane >> 3);
-  p.sx = tx * 8 + (lane & 7);
-  p.live = p.sy < a.h && p.sx < a.w;
-  p.pix = min(p.sy, a.h - 1) * a.w + min(p.sx, a.w - 1);
-  return p;
-}
-__device__ __forceinline__ float2 dm_coords(const DmArgs& a, const DmUnit& u, const DmPixel& p, bool on) {
-  const int HW = a.h * a.w;
-  float2 c;
-  if (a.coords_xy) c = *reinterpret_cast<const float2*>(a.coords + ((size_t)u.n * HW + p.pix) * 2);
-  else c = make_float2(a.coords[((size_t)u.n * 2 + 0) * HW + p.pix], a.coords[((size_t)u.n * 2 + 1) * HW + p.pix]);
-  if (!(on && p.live)) { c.x = -1.0e6f; c.y = -1.0e6f; }          // padding lanes: every tap out of range, no memory access
-  return c;
 }
 
 #ifdef EXP_DM_TIMESTAMPS
@@ -586,112 +556,31 @@ __global__ __launch_bounds__(256, 2) void corr_dm_encode_kernel(DmArgs a) {
 // with the flow encoder's convolutions for more than they save.)
 // ---------------------------------------------------------------------------------------------------------------------
 // Builder: all-pairs <f1/4, f2/4> (fp16 GEMM, fp32 accumulate, rounded to fp16) + three avg_pool2d levels, written in the
-// displacement-major layout.  Workgroup = half a source tile (4 x 8 pixels) x 8 aligned target rows: level 0 on the matrix
-// cores into LDS R[px][8 rows][W8], the pooled levels reduced in LDS from the fp16 values of the level below (what
-// avg_pool2d of the fp16 volume computes), then every (pixel, target) value is emitted to its line: a thread gathers the 8
-// pixels of one tile row that share (dy, dx) and writes their 16 bytes.
+// displacement-major layout.  Workgroup = half a source tile (4 x 8 pixels) x 8 aligned target rows: the four levels are
+// computed in LDS by the front half shared with the tiled builder (corr_pyramid.hiph), then every (pixel, target) value is
+// emitted to its line: a thread gathers the 8 pixels of one tile row that share (dy, dx) and writes their 16 bytes.
 // ---------------------------------------------------------------------------------------------------------------------
-struct DmBuildArgs {
-  const _Float16* f;          // [F][HW][128] channels-last feature maps, already scaled by 1/4
-  const int64_t* ii; const int64_t* jj;
-  const int* slot;
-  _Float16* lvl[4];
-  int h, w, ntx, nty, num_levels;
-};
+typedef CorrPad<4, 2, 2, 2> DmPad;      // the emission reads one target of 8 neighbouring pixels: spread their rows over the banks
 
-__device__ __forceinline__ unsigned pk2h(_Float16 a, _Float16 b) {
-  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
-__device__ __forceinline__ _Float16 pool4h(_Float16 a, _Float16 b, _Float16 c, _Float16 d) {
-  // avg_pool2d on half: float accumulation over (0,0),(0,1),(1,0),(1,1), times 1/4, rounded to half
-  const float s = (((float)a + (float)b) + (float)c) + (float)d;
-  return (_Float16)(s * 0.25f);
-}
-
-__global__ __launch_bounds__(256, 2) void corr_dm_build_kernel(DmBuildArgs a) {
-  constexpr int C = 128, PX = 32;
+__global__ __launch_bounds__(256, 2) void corr_dm_build_kernel(CorrBuildArgs a) {
   extern __shared__ __attribute__((aligned(16))) _Float16 bsm[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int col = lane & 15, kg = lane >> 4;
-  const int h = a.h, w = a.w, HW = h * w;
+  const int tid = threadIdx.x;
+  const int h = a.h, w = a.w;
   const int e = blockIdx.z, grp = blockIdx.y;
   const int tile = blockIdx.x >> 1, half = blockIdx.x & 1;
   const int tyi = tile / a.ntx, txi = tile - tyi * a.ntx;
   const int ntiles = a.ntx * a.nty;
-  const int fi = (int)a.ii[e], fj = (int)a.jj[e];
   const size_t sl = (size_t)a.slot[e];
-  const int W8 = ((w + 7) >> 3) << 3;
-  const int w1 = w >> 1, w2 = w >> 2, w3 = w >> 3, h1 = h >> 1, h2 = h >> 2, h3 = h >> 3;
-  const int W81 = ((w1 + 7) >> 3) << 3, W82 = ((w2 + 7) >> 3) << 3, W83 = ((w3 + 7) >> 3) << 3;
-  const int RS = 8 * W8 + 4, L1S = 4 * W81 + 2, L2S = 2 * W82 + 2, L3S = W83 + 2;   // per-pixel strides (padded: bank spread)
-  _Float16* R = bsm;
-  _Float16* L1 = R + PX * RS;
-  _Float16* L2 = L1 + PX * L1S;
-  _Float16* L3 = L2 + PX * L2S;
-
-  // B operand: the 32 source pixels of this half tile (row syh = k >> 3 of the half, column k & 7), clamped into the map
-  f16x8 bfrag[2][4];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int k = nt * 16 + col;
-    const int sy = min(tyi * 8 + half * 4 + (k >> 3), h - 1), sx = min(txi * 8 + (k & 7), w - 1);
-    const f16x8* src = reinterpret_cast<const f16x8*>(a.f + ((size_t)fi * HW + sy * w + sx) * C + kg * 8);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) bfrag[nt][kk] = src[kk * 4];
-  }
-  // ---- level 0: targets t = local row * W8 + x of rows 8 grp .. 8 grp + 7 ----
-  const int ntile = (8 * W8) >> 4;
-  const _Float16* f2 = a.f + (size_t)fj * HW * C;
-  for (int t16 = wv; t16 < ntile; t16 += 4) {
-    const int t = t16 * 16 + col;
-    const int ly = t / W8, x = t - ly * W8, y = 8 * grp + ly;
-    const bool ok = y < h && x < w;
-    const f16x8* src = reinterpret_cast<const f16x8*>(f2 + ((size_t)(ok ? y * w + x : 0)) * C + kg * 8);
-    f16x8 af[4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) af[kk] = src[kk * 4];
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) if (!ok) af[kk] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[kk], bfrag[nt][kk], acc, 0, 0, 0);
-      *reinterpret_cast<uint2*>(R + (nt * 16 + col) * RS + t16 * 16 + kg * 4) =
-          make_uint2(pk2h((_Float16)acc[0], (_Float16)acc[1]), pk2h((_Float16)acc[2], (_Float16)acc[3]));
-    }
-  }
-  __syncthreads();
-  // ---- pooled levels in LDS (each from the fp16 values of the level below) ----
-  if (a.num_levels > 1) {
-    for (int idx = tid; idx < PX * 4 * W81; idx += 256) {
-      const int px = idx / (4 * W81), r = idx - px * (4 * W81), y = r / W81, x = r - y * W81;
-      const _Float16* s = R + px * RS + (2 * y) * W8 + 2 * x;
-      L1[px * L1S + r] = (x < w1) ? pool4h(s[0], s[1], s[W8], s[W8 + 1]) : (_Float16)0.0f;
-    }
-    __syncthreads();
-  }
-  if (a.num_levels > 2) {
-    for (int idx = tid; idx < PX * 2 * W82; idx += 256) {
-      const int px = idx / (2 * W82), r = idx - px * (2 * W82), y = r / W82, x = r - y * W82;
-      const _Float16* s = L1 + px * L1S + (2 * y) * W81 + 2 * x;
-      L2[px * L2S + r] = (x < w2) ? pool4h(s[0], s[1], s[W81], s[W81 + 1]) : (_Float16)0.0f;
-    }
-    __syncthreads();
-  }
-  if (a.num_levels > 3) {
-    for (int idx = tid; idx < PX * W83; idx += 256) {
-      const int px = idx / W83, x = idx - px * W83;
-      const _Float16* s = L2 + px * L2S + 2 * x;
-      L3[px * L3S + x] = (x < w3) ? pool4h(s[0], s[1], s[W82], s[W82 + 1]) : (_Float16)0.0f;
-    }
-    __syncthreads();
-  }
+  // the 32 source pixels of this half tile (row k >> 3 of the half, column k & 7), clamped into the map
+  const CorrPyramidLds py = corr_pyramid_lds<DmPad>(a.f, (int)a.ii[e], (int)a.jj[e], h, w, grp, a.num_levels, bsm, [&](int k) {
+    return min(tyi * 8 + half * 4 + (k >> 3), h - 1) * w + min(txi * 8 + (k & 7), w - 1);
+  });
   // ---- emission: segment = (source row syh of the half tile, local target row r, displacement-column PAIR dx2) -> the 32
   // bytes of 8 lanes x 2 columns (the inverse of dx = (tx - sxl + cx) mod wp; a displacement that names the padding column
   // of an odd width stores a zero)
-  auto emit = [&](const _Float16* src, int stride, int Wp, int lvl, int rows, int hl, int wl) {
+  auto emit = [&](int lvl) {
+    const _Float16* src = py.lvl[lvl];
+    const int stride = py.stride[lvl], Wp = py.W[lvl], rows = 8 >> lvl, hl = h >> lvl, wl = w >> lvl;
     const int cy = hl >> 1, cx = wl >> 1;
     const int wp = (wl + 1) & ~1, wp2 = wp >> 1;
     const int y0 = (8 * grp) >> lvl;
@@ -714,17 +603,17 @@ __global__ __launch_bounds__(256, 2) void corr_dm_build_kernel(DmBuildArgs a) {
           txl = txl < 0 ? txl + wp : (txl >= wp ? txl - wp : txl);
           v[sub] = txl < wl ? src[(syh * 8 + lx) * stride + r * Wp + txl] : (_Float16)0.0f;
         }
-        o[lx >> 2][lx & 3] = pk2h(v[0], v[1]);
+        o[lx >> 2][lx & 3] = h_pack(v[0], v[1]);
       }
       u32x4* out = reinterpret_cast<u32x4*>(dst + (((size_t)dy * wp2 + dx2) * 64 + (half * 4 + syh) * 8) * 2);
       out[0] = o[0];
       out[1] = o[1];
     }
   };
-  emit(R, RS, W8, 0, 8, h, w);
-  if (a.num_levels > 1) emit(L1, L1S, W81, 1, 4, h1, w1);
-  if (a.num_levels > 2) emit(L2, L2S, W82, 2, 2, h2, w2);
-  if (a.num_levels > 3) emit(L3, L3S, W83, 3, 1, h3, w3);
+  emit(0);
+  if (a.num_levels > 1) emit(1);
+  if (a.num_levels > 2) emit(2);
+  if (a.num_levels > 3) emit(3);
 }
 
 }  // namespace glorie
@@ -739,30 +628,12 @@ extern "C" long glorie_corr_dm_level_halfs(int h, int w, int level) {
 
 extern "C" int glorie_corr_dm_build(const void* fmaps_cl, const int64_t* ii, const int64_t* jj, const int* slots,
                                     void* const* levels, int num_levels, int n_new, int h, int w, int C, void* stream) {
-  if (n_new < 0 || h <= 0 || w <= 0 || num_levels < 1 || num_levels > 4) return GLORIE_EINVAL;
-  if (n_new == 0) return GLORIE_OK;
-  if (!fmaps_cl || !ii || !jj || !slots || !levels) return GLORIE_EINVAL;
-  if (C != 128 || (h >> (num_levels - 1)) < 1 || (w >> (num_levels - 1)) < 1) return GLORIE_EUNSUPPORTED;
-  DmBuildArgs a{};
-  a.f = reinterpret_cast<const _Float16*>(fmaps_cl);
-  a.ii = ii; a.jj = jj; a.slot = slots; a.h = h; a.w = w; a.num_levels = num_levels;
-  a.ntx = (w + 7) / 8; a.nty = (h + 7) / 8;
-  for (int l = 0; l < num_levels; ++l) {
-    if (!levels[l]) return GLORIE_EINVAL;
-    a.lvl[l] = reinterpret_cast<_Float16*>(levels[l]);
-  }
-  auto pad8 = [](int v) { return ((v + 7) >> 3) << 3; };
-  const size_t lds = sizeof(_Float16) * 32 *
-                     (size_t)((8 * pad8(w) + 4) + (4 * pad8(w >> 1) + 2) + (2 * pad8(w >> 2) + 2) + (pad8(w >> 3) + 2));
-  if (lds > 80 * 1024) return GLORIE_EUNSUPPORTED;
   static PerDeviceOnce attr;
-  if (attr.first()) {
-    GLORIE_TRY(check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_dm_build_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)));
-  }
-  const dim3 grid(a.ntx * a.nty * 2, (h + 7) / 8, n_new);
-  hipLaunchKernelGGL(corr_dm_build_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
-  return check_launch();
+  return corr_build_launch<DmPad>(corr_dm_build_kernel, attr, fmaps_cl, ii, jj, slots, levels, num_levels, n_new, h, w, C,
+                                  stream, [&] {     // a workgroup = half a source tile; the last level must not be empty
+                                    const bool ok = (h >> (num_levels - 1)) >= 1 && (w >> (num_levels - 1)) >= 1;
+                                    return ok ? ((w + 7) / 8) * ((h + 7) / 8) * 2 : 0;
+                                  });
 }
 
 extern "C" int glorie_corr_dm_lookup(const void* const* levels, const int* slots, const float* coords, int coords_xy, int N,

@@ -6,70 +6,27 @@
 // without ever materialising the 61 MB/edge correlation volume whose per-pixel planes make the
 // windowed gather fetch 4.3x its useful bytes (profiles/r01_pmc_gathers.json).
 //
-// Structure.  A workgroup owns an 8 x 8 block of source pixels, each of its four waves a 4 x 4 sub-block
-// (a 16 x 1 run of pixels has a ~23 x 8 bounding box at level 0, a 4 x 4 block ~11 x 11: a third fewer
-// targets to multiply and to pull through L2); the wave's four 16-byte A fragments (128
-// channels) stay in registers.  Per level the wave takes the bounding box of the 16 windows
-// (smooth flow -> ~11 x 11 target pixels at level 0), evaluates the dense 16 x |bbox| block of dot
-// products with v_mfma_f32_16x16x32_f16 (B fragments are 16-byte channel runs of the pooled,
-// channel-last feature map, L2 resident), rounds to fp16 like the reference volume and parks it in
-// LDS; every pixel then picks and blends its own window from LDS with the reference's fp16
-// rounding sequence.  If the 16 windows do not share a compact bbox (bbox > 256 targets: flow
-// discontinuities, random coords) the wave falls back to one 8x8 bbox per pixel -- 16x the MFMA
-// work for that tile, still correct.  Outputs of the 4 levels are staged in LDS and written as
-// 16-byte runs (8 pixels of a block row) per channel.
+// One kernel, corr_otf8_kernel: a workgroup owns an 8 x 8 block of source pixels that shares ONE target box per level; the
+// dense block of dot products is evaluated with v_mfma_f32_16x16x32_f16, rounded to fp16 like the reference volume and
+// parked in LDS, from where every pixel blends its own window (the comment above the kernel has the details).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include "common.hiph"
+#include "corr_common.hiph"
 
 namespace glorie {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-
-constexpr int kOtfCap = 256;            // max targets of a shared bbox
-constexpr int kOtfLdR = kOtfCap + 8;    // fp16 elements per source-pixel row of the result buffer
-constexpr int kOtfPx = 64;              // source pixels per workgroup (4 waves x 16)
-constexpr int kOtfLdO = kOtfPx + 8;
 
 struct OtfLevels {
   const _Float16* f2[4];   // [frames][h_l*w_l][C] channel-last, pooled, pre-scaled by 1/4
   int h[4], w[4];
 };
 
-__device__ __forceinline__ _Float16 otf_blend4(_Float16 s00, _Float16 s01, _Float16 s10, _Float16 s11,
-                                               _Float16 w00, _Float16 w01, _Float16 w10, _Float16 w11) {
-#pragma clang fp contract(off)
-  _Float16 acc = (_Float16)0.0f;
-  _Float16 t;
-  t = s00 * w00; acc = acc + t;
-  t = s01 * w01; acc = acc + t;
-  t = s10 * w10; acc = acc + t;
-  t = s11 * w11; acc = acc + t;
-  return acc;
-}
-__device__ __forceinline__ _Float16 otf_weight(float prod) {
-  asm volatile("" : "+v"(prod));   // keep the fp32 rounding step (see corr.hip: weight_cast)
-  return (_Float16)prod;
-}
-
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-  return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 // =====================================================================================================
 // 8x8 source tiles sharing ONE target box per level ("otf8").
 //
-// Round 1's 4x4-per-wave kernel (removed in round 4) pulled every target row through L2 once per wave: ~6 KB of features per
-// source pixel (1.55 GB of L2 traffic per G8 lookup).  Here a workgroup owns an 8 x 8 block of source pixels
+// A 4x4-block-per-wave kernel (round 1, removed in round 4) pulled every target row through L2 once per wave: ~6 KB of features
+// per source pixel (1.55 GB of L2 traffic per G8 lookup).  Here a workgroup owns an 8 x 8 block of source pixels
 // and ALL of it shares the bounding box of its 64 windows (smooth flow: 16 x 16 targets at level 0, 12 x 12,
 // 10 x 10, 9 x 9 above: 581 target rows = 2.3 KB per source pixel).  The four waves split the box's 16-target
 // tiles; a wave loads a tile's rows once (A operand, straight from L2 into registers, the next tile in
@@ -91,20 +48,10 @@ constexpr int kLdR8 = kCap8 + 4;        // halfs per pixel row of R: 162 dwords 
 constexpr int kEncK = 224;              // 4 levels x 7 rows x 8 (7 taps + pad): K of the fused encoder
 constexpr int kLdT8 = kEncK + 8;        // halfs per pixel row of T: 116 dwords -> conflict-free b128 reads
 
-__device__ __forceinline__ unsigned otf_dpp_next(unsigned v) {
-  // lane i <- lane i+1 inside a row of 16 lanes (row_shl:1)
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true);
-}
-__device__ __forceinline__ _Float16 h_lo(unsigned v) { return __builtin_bit_cast(_Float16, (unsigned short)(v & 0xffffu)); }
-__device__ __forceinline__ _Float16 h_hi(unsigned v) { return __builtin_bit_cast(_Float16, (unsigned short)(v >> 16)); }
-__device__ __forceinline__ unsigned h_pack(_Float16 a, _Float16 b) {
-  return (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-}
-
 // wave64 min / max without LDS: four row_shr steps reduce every row of 16 lanes into its last lane, row_bcast:15
 // and row_bcast:31 carry the row results along (lane 63 ends up with all 64), v_readlane broadcasts.  The
-// __shfl_xor butterflies of the 4x4 kernel above are ds_bpermute round trips: 24 dependent ones per level were
-// 3.7k cycles of pure latency per workgroup here.
+// __shfl_xor butterflies are ds_bpermute round trips: 24 dependent ones per level were 3.7k cycles of pure latency per
+// workgroup here.
 template <bool IS_MIN>
 __device__ __forceinline__ int wave_reduce_dpp(int v) {
   const int ident = IS_MIN ? 0x7fffffff : (int)0x80000000;
@@ -290,11 +237,9 @@ __global__ __launch_bounds__(256, 2) void corr_otf8_kernel(
       if (enc.dbg & 2) break;
       const int px = epx[r];
       const float xs = fminf(fmaxf(exc[r] * inv, -1.0e6f), 1.0e6f), ys = fminf(fmaxf(eyc[r] * inv, -1.0e6f), 1.0e6f);
-      const float fx = floorf(xs), fy = floorf(ys);
-      const float dx = xs - fx, dy = ys - fy;
-      const int eix = static_cast<int>(fx) - 3, eiy = static_cast<int>(fy) - 3;
-      const _Float16 w00 = otf_weight((1.0f - dx) * (1.0f - dy)), w01 = otf_weight((1.0f - dx) * dy);
-      const _Float16 w10 = otf_weight(dx * (1.0f - dy)), w11 = otf_weight(dx * dy);
+      const CorrWindow win = corr_window(xs, ys);
+      const int eix = win.ix0, eiy = win.iy0;
+      const CorrWeights<_Float16> wt = corr_weights<_Float16>(win.dx, win.dy);
       const bool member = mode == 0 || (mode == 1 ? ((((px >> 5) & 1) == (qd >> 1)) && (((px >> 2) & 1) == (qd & 1)))
                                                   : (px == single_px));
       // first half of this lane's window row inside R[px]; non-members read a harmless in-range spot
@@ -305,12 +250,12 @@ __global__ __launch_bounds__(256, 2) void corr_otf8_kernel(
         d0 = __builtin_amdgcn_alignbit(d1, d0, 16); d1 = __builtin_amdgcn_alignbit(d2, d1, 16);
         d2 = __builtin_amdgcn_alignbit(d3, d2, 16); d3 = __builtin_amdgcn_alignbit(d4, d3, 16);
       }
-      const unsigned n0 = otf_dpp_next(d0), n1 = otf_dpp_next(d1), n2 = otf_dpp_next(d2), n3 = otf_dpp_next(d3);
+      const unsigned n0 = dpp_next(d0), n1 = dpp_next(d1), n2 = dpp_next(d2), n3 = dpp_next(d3);
       const _Float16 sv[8] = {h_lo(d0), h_hi(d0), h_lo(d1), h_hi(d1), h_lo(d2), h_hi(d2), h_lo(d3), h_hi(d3)};
       const _Float16 nx[8] = {h_lo(n0), h_hi(n0), h_lo(n1), h_hi(n1), h_lo(n2), h_hi(n2), h_lo(n3), h_hi(n3)};
       _Float16 o[8];
 #pragma unroll
-      for (int i = 0; i < 7; ++i) o[i] = otf_blend4(sv[i], nx[i], sv[i + 1], nx[i + 1], w00, w01, w10, w11);
+      for (int i = 0; i < 7; ++i) o[i] = blend4(sv[i], nx[i], sv[i + 1], nx[i + 1], wt);
       o[7] = (_Float16)0.0f;
       if (member && row < 7) {
         uint4 pk = make_uint4(h_pack(o[0], o[1]), h_pack(o[2], o[3]), h_pack(o[4], o[5]), h_pack(o[6], o[7]));
@@ -450,6 +395,15 @@ static int otf_levels(const void* const* fmap2_levels, int num_levels, int h, in
   return GLORIE_OK;
 }
 
+// instrumentation builds only (tools/otf_timeline.py): ablation switches and the stamp buffer from the environment
+static void otf_debug_env(OtfEnc& enc) {
+#ifdef EXP_OTF_DBG
+  enc.dbg = getenv("GLORIE_OTF_DBG") ? atoi(getenv("GLORIE_OTF_DBG")) : 0;
+  enc.stamps = getenv("GLORIE_OTF_STAMPS") ? (unsigned long long*)strtoull(getenv("GLORIE_OTF_STAMPS"), nullptr, 0) : nullptr;
+  if (!enc.stamps) enc.dbg &= ~32;
+#endif
+}
+
 constexpr size_t kOtf8Lds = sizeof(_Float16) * (64 * kLdR8 + 8 + 64 * kLdT8);
 
 template <bool WC, bool EN>
@@ -476,11 +430,7 @@ extern "C" int glorie_corr_otf(const void* fmap1, const void* const* fmap2_level
   OtfLevels lv{};
   GLORIE_TRY(otf_levels(fmap2_levels, num_levels, h, w, lv));
   OtfEnc e0{};
-#ifdef EXP_OTF_DBG                         // instrumentation builds only (tools/otf_timeline.py)
-  e0.dbg = getenv("GLORIE_OTF_DBG") ? atoi(getenv("GLORIE_OTF_DBG")) : 0;
-  e0.stamps = getenv("GLORIE_OTF_STAMPS") ? (unsigned long long*)strtoull(getenv("GLORIE_OTF_STAMPS"), nullptr, 0) : nullptr;
-  if (!e0.stamps) e0.dbg &= ~32;
-#endif
+  otf_debug_env(e0);
   return launch_otf8<true, false>(fmap1, lv, num_levels, coords, ii, jj, out, N, h, w, e0, (hipStream_t)stream);
 }
 
@@ -495,11 +445,7 @@ extern "C" int glorie_corr_otf_encode(const void* fmap1, const void* const* fmap
   OtfLevels lv{};
   GLORIE_TRY(otf_levels(fmap2_levels, num_levels, h, w, lv));
   OtfEnc enc{reinterpret_cast<const _Float16*>(enc_w), enc_b, reinterpret_cast<_Float16*>(enc_out), enc_stride, 0, nullptr};
-#ifdef EXP_OTF_DBG
-  enc.dbg = getenv("GLORIE_OTF_DBG") ? atoi(getenv("GLORIE_OTF_DBG")) : 0;
-  enc.stamps = getenv("GLORIE_OTF_STAMPS") ? (unsigned long long*)strtoull(getenv("GLORIE_OTF_STAMPS"), nullptr, 0) : nullptr;
-  if (!enc.stamps) enc.dbg &= ~32;
-#endif
+  otf_debug_env(enc);
   if (corr_out)
     return launch_otf8<true, true>(fmap1, lv, num_levels, coords, ii, jj, corr_out, N, h, w, enc, (hipStream_t)stream);
   return launch_otf8<false, true>(fmap1, lv, num_levels, coords, ii, jj, nullptr, N, h, w, enc, (hipStream_t)stream);

@@ -35,6 +35,18 @@ def timeit(fn, reps=20, batches=5):
     return sorted(ts)[len(ts) // 2]
 
 
+def _rebuild(arena, fmaps_cl, fi, fj):
+    """the builder of `arena`'s layout writing its current edges into the slots they already own"""
+    import ctypes
+    from glorie_slam_amd import _lib as L
+    fn = L.load().glorie_corr_dm_build if arena.layout == "dm" else L.load().glorie_corr_build
+    fi, fj, lv = fi.contiguous(), fj.contiguous(), arena.views()
+    arr = (ctypes.c_void_p * len(lv))(*[t.data_ptr() for t in lv])
+    return lambda: L.check(fn(L.ptr(fmaps_cl), L.ptr(fi), L.ptr(fj), L.ptr(arena.slots), ctypes.cast(arr, ctypes.c_void_p),
+                              len(lv), int(fi.shape[0]), arena.h, arena.w, int(fmaps_cl.shape[-1]), L.stream_ptr()),
+                           "glorie_corr_build")
+
+
 def main():
     dev = torch.device("cuda", 0)
     g, video, graph = bench.build_graph(dev)
@@ -59,9 +71,12 @@ def main():
                                             terms=bias0, act=U.ACT_RELU))
     t_dm = timeit(lambda: arenas["dm"](coords1, channels_last=True))
     t_dm_enc = timeit(lambda: arenas["dm"].lookup_encode(coords1, w_dm, bias0, c1))
+    t_build = {lay: timeit(_rebuild(arenas[lay], blk0.levels[0], rig * graph.ii, rig * graph.jj + c), reps=5) for lay in arenas}
     for name, t in (("tiled gather (channels-last)", t_vol), ("tiled gather + 1x1 encoder launch", t_vol_enc),
                     ("displacement-major gather", t_dm), ("displacement-major gather + encoder", t_dm_enc)):
         print(f"{name:38s} {t:8.1f} us   {alg / t / 1e6:7.2f} TB/s of algorithmic bytes   frac {alg / t / 1e6 / 8.0:.3f}")
+    for lay, name in (("tiled", "tiled builder"), ("dm", "displacement-major builder")):
+        print(f"{name:38s} {t_build[lay]:8.1f} us   ({N} edges, all four levels)")
     if os.environ.get("CORR_ONLY_VOLUME"):
         return
     fm = video.fmaps
