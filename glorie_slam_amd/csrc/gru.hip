@@ -490,7 +490,10 @@ extern "C" int glorie_update_bookkeeping(const float* coords1, const float* delt
                                          void* stream) {
   if (n_target < 0 || G < 0 || HW <= 0 || n_edges < 0) return GLORIE_EINVAL;
   const long n_eta = (long)G * HW;
-  const long n = n_target > n_eta ? n_target : n_eta;
+  // one thread per element of the LONGEST of the three jobs: the ages are incremented whatever the other two sizes are
+  const long n_age = age ? (long)n_edges : 0;
+  long n = n_target > n_eta ? n_target : n_eta;
+  if (n_age > n) n = n_age;
   if (n == 0) return GLORIE_OK;
   if ((n_target && (!coords1 || !delta || !target)) || (n_eta && (!eta || !frames || !damping_table || !damping_ba)))
     return GLORIE_EINVAL;

@@ -188,7 +188,10 @@ int glorie_altcorr_fwd(const float* fmap1, const float* fmap2, const float* coor
  *   (BA damping 0.2 * damping + EP), :256 (age += 1)
  * coords1 / delta / target: n_target floats ([N,h,w,2]); eta [G,HW] = the operator's damping output for the G frames
  * `frames` (int64 [G]); damping_table [B,HW] receives the rows, damping_ba [G,HW] = 0.2 * eta + ep (each op rounded
- * separately, as the torch chain); age int64 [n_edges] is incremented (may be NULL). */
+ * separately, as the torch chain); age int64 [n_edges] is incremented (may be NULL).
+ * The three jobs are independent: the launch covers max(n_target, G*HW, n_edges) elements, so every one of the n_edges ages
+ * is incremented also where n_edges exceeds both other sizes or both are 0 (G = 0 and n_target = 0 with ages is a valid
+ * call).  Rows of damping_table that `frames` does not name are not touched; `frames` need not be sorted. */
 int glorie_update_bookkeeping(const float* coords1, const float* delta, float* target, long n_target,
                               const float* eta, const int64_t* frames, float* damping_table, float* damping_ba,
                               int G, int HW, float ep, int64_t* age, int n_edges, void* stream);
