@@ -125,6 +125,11 @@ SIGNATURES = {
                           + [_c_f, _c_f, _c_int] + [_c_f] * 4 + [_vp, _vp, _vp]),
     "glorie_iproj_dirty": (_c_int, [_vp] * 5 + [_c_int] * 3 + [_vp, _vp, _c_int, _vp]),
     "glorie_proxy_depth": (_c_int, [_vp, _vp] + [_c_int] * 4 + [_vp] + [_c_f] * 4 + [_vp] * 5),
+    "glorie_ms_ssim_workspace": (_sz, [_c_int, _c_int, _c_int]),
+    "glorie_ms_ssim": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "glorie_frame_reduce_workspace": (_sz, [_c_int, _c_int]),
+    "glorie_frame_reduce": (_c_int, [_vp, _vp, _c_int, _c_int] + [_vp] * 7),
+    "glorie_mask_apply": (_c_int, [_vp, _c_int, _c_int] + [_vp] * 7),
 }
 
 _lib = None

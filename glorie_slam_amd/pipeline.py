@@ -601,6 +601,13 @@ class SequenceRunner:
         return {"keyframes": int(self.video.counter.value), "final_ba_edges": int(n_edges), "mapped": self.mapped,
                 "points": int(self.npc.pts_num()), "losses": list(self.losses), "timing": self.timing}
 
+    # ---- eval_render.py:18-124 ------------------------------------------------------------------------------------------
+    def evaluate(self, output=None, gt_depth_fn=None, **kwargs):
+        """re-render every mapped keyframe and score it against its image (eval_render.eval_kf_imgs: PSNR, MS-SSIM, their
+        masked forms, depth L1 with gt_depth_fn; the masked maps and the metrics file under `output`).  Not part of run()"""
+        from .eval_render import eval_kf_imgs
+        return eval_kf_imgs(self, output=output, gt_depth_fn=gt_depth_fn, **kwargs)
+
 
 # ---- the synthetic 640x480 stream of the config-3 test and of bench.py's `sequence` entry --------------------------------
 def synthetic_cfg(device, buffer, H=480, W=640):

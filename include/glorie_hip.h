@@ -874,6 +874,42 @@ int glorie_proxy_depth(const float* full_pcl, const uint8_t* full_mask, int coun
                        const float* w2c, float fx, float fy, float cx, float cy, const float* droid_depth,
                        const float* mono_depth, float* zbuf, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Image-quality metrics of the re-render evaluation                                     */
+/* ------------------------------------------------------------------------------------ */
+
+/* MS-SSIM with the defaults of pytorch_msssim   reference: src/utils/eval_render.py:62, :83
+ * x, y f32 in [0,1], [H,W,3] (channels_first 0) or [3,H,W] (1).  data_range 1, K = (0.01, 0.03); the window is 11 taps
+ * exp(-(i-5)^2 / (2 1.5^2)) normalised to sum 1, applied separably as a valid convolution.  Per level and channel
+ * cs = mean((2 s12 + C2) / (s1 + s2 + C2)), ssim = mean((2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs_map) over the
+ * (h-10) x (w-10) valid region; between levels avg_pool2d(2, 2, padding = size % 2 per axis, count_include_pad).
+ * `levels` in [1, 5] takes the first `levels` of the weights (0.0448, 0.2856, 0.3001, 0.2363, 0.1333): per channel
+ * prod_{l < levels-1} relu(cs_l)^w_l * relu(ssim_{levels-1})^w_{levels-1}, then the mean over the channels.
+ * out f32 [1 + 2 levels]: out[0] the result, out[1 + 2l], out[2 + 2l] the channel means of ssim and cs of level l.
+ * A level with a side below 11 is GLORIE_EINVAL (the 160-pixel rule of the library for 5 levels is the caller's).
+ * Moments and sums in fp64; per-workgroup partials added in a fixed order (no float atomics: bitwise repeatable).
+ * workspace: glorie_ms_ssim_workspace(H, W, levels) bytes (0: invalid sizes).  levels + 1 launches, no host
+ * synchronisation. */
+size_t glorie_ms_ssim_workspace(int H, int W, int levels);
+int glorie_ms_ssim(const float* x, const float* y, int H, int W, int channels_first, int levels, void* workspace,
+                   float* out, void* stream);
+/* The sums of one evaluated frame   reference: src/utils/eval_render.py:59-61, :71, :80-82
+ * color_a, color_b f32 [H,W,3]; mask [H,W] u8 or NULL; depth, gt_depth f32 [H,W] or NULL.  fp32 differences, squared
+ * and accumulated in fp64.  out f32 [3] = { psnr = -10 log10(mean squared difference over H W 3),
+ * masked_psnr = the same over the pixels of the mask (NaN on an empty or NULL mask, as mse_loss of an empty selection),
+ * depth_l1 = mean |depth - gt_depth| over the mask (0 without both depths; NaN on an empty mask) };
+ * count int32 [1] (or NULL) = pixels of the mask.  workspace: glorie_frame_reduce_workspace(H, W) bytes.  Two
+ * launches, fixed summation order (bitwise repeatable), no host synchronisation. */
+size_t glorie_frame_reduce_workspace(int H, int W);
+int glorie_frame_reduce(const float* color_a, const float* color_b, int H, int W, const unsigned char* mask,
+                        const float* depth, const float* gt_depth, void* workspace, float* out, int* count,
+                        void* stream);
+/* x[~mask] = 0 on copies   reference: src/utils/eval_render.py:72-74
+ * depth [H,W], color_a, color_b [H,W,3] f32 -> the outputs of the same shapes, 0 where mask [H,W] u8 is 0 (whatever
+ * the input holds there); each output is written only when not NULL; the inputs are not modified.  One launch. */
+int glorie_mask_apply(const unsigned char* mask, int H, int W, const float* depth, const float* color_a,
+                      const float* color_b, float* depth_out, float* color_a_out, float* color_b_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
