@@ -130,6 +130,14 @@ SIGNATURES = {
     "glorie_frame_reduce_workspace": (_sz, [_c_int, _c_int]),
     "glorie_frame_reduce": (_c_int, [_vp, _vp, _c_int, _c_int] + [_vp] * 7),
     "glorie_mask_apply": (_c_int, [_vp, _c_int, _c_int] + [_vp] * 7),
+    "glorie_tsdf_allocate_workspace": (_sz, [ctypes.c_long]),
+    "glorie_tsdf_allocate": (_c_int, [_vp, _c_int, _c_int, _vp] + [_c_f] * 6 + [_vp, _c_f, _vp, _vp, _vp, _c_int, _vp, _vp,
+                                      ctypes.POINTER(_c_int), _vp]),
+    "glorie_tsdf_integrate": (_c_int, [_vp, _vp, _c_int, _c_int, _vp] + [_c_f] * 6 + [_vp, _c_f, _vp, _vp, _c_int]
+                              + [_vp] * 5),
+    "glorie_tsdf_extract_workspace": (_sz, [ctypes.c_long, _c_int]),
+    "glorie_tsdf_extract_count": (_c_int, [_vp, _c_f, _vp, _vp, _c_int, _vp, _vp, _vp, ctypes.POINTER(_c_int), _vp]),
+    "glorie_tsdf_extract_emit": (_c_int, [_vp, ctypes.c_double, _vp, _vp, _c_int] + [_vp] * 8),
 }
 
 _lib = None

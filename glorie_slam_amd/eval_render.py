@@ -11,9 +11,9 @@ Both return {"frames": [{"video_idx", "tstamp", "psnr", "ms_ssim", "masked_psnr"
 The per-frame values stay on the device and are read back once at the end; the runner, its images and the cloud are only
 read.
 
-Out of scope: LPIPS (torchmetrics' AlexNet weights come from the network), the PNG copies of the renders (cv2) and the
-mesh extraction that reads the saved maps (Open3D's scalable TSDF); the metrics files keep the reference's names and line
-order minus the LPIPS lines.
+Out of scope: LPIPS (torchmetrics' AlexNet weights come from the network) and the PNG copies of the renders (cv2); the
+metrics files keep the reference's names and line order minus the LPIPS lines.  The mesh that reads the saved maps:
+generate_mesh.py.
 """
 import os
 import shutil

@@ -9,8 +9,7 @@ src/utils/eval_render.py:59-89, which calls pytorch_msssim.ms_ssim and torch's m
 Every sum is accumulated in fp64 from per-workgroup partials in a fixed order: repeated calls are bitwise equal, nothing
 reads the device back, and every call records into a hipGraph.  Results are 0-dim float32 device tensors.
 
-Out of scope: LPIPS (torchmetrics' AlexNet weights come from the network), the PNG copies of the renders (cv2) and mesh
-extraction (Open3D's scalable TSDF).
+Out of scope: LPIPS (torchmetrics' AlexNet weights come from the network) and the PNG copies of the renders (cv2).
 """
 import torch
 

@@ -608,6 +608,28 @@ class SequenceRunner:
         from .eval_render import eval_kf_imgs
         return eval_kf_imgs(self, output=output, gt_depth_fn=gt_depth_fn, **kwargs)
 
+    # ---- generate_mesh.py:55-123 ----------------------------------------------------------------------------------------
+    def mesh(self, output=None, mesh_name_suffix="kf", scene="scene", **kwargs):
+        """the triangle mesh of the run (generate_mesh.fuse_frames): every mapped keyframe is re-rendered (eval_kf_imgs)
+        and its masked depth and colour are fused from device memory into a TSDF volume with the keyframe's own pose;
+        kwargs: scale, transform, voxel_length, sdf_trunc, max_blocks.  -> (vertices f32 [V,3], colors f32 [V,3], faces
+        int32 [F,3]) on the device; with `output` also mesh/{scene}_{suffix}.ply and mesh/vertices_pos_{suffix}.npy, as
+        generate_mesh_kf writes from the files of evaluate(output) and save_video.  Not part of run()"""
+        from .eval_render import eval_kf_imgs
+        from .generate_mesh import fuse_frames, save_mesh
+        res = eval_kf_imgs(self, keep_renders=True)
+        frames = []
+        for f in res["frames"]:
+            r = f["render"]
+            depth = torch.where(r["mask"], r["depth"].float(), torch.zeros_like(r["depth"], dtype=torch.float32))
+            color = torch.where(r["mask"][..., None], r["color"].float(), torch.zeros_like(r["color"], dtype=torch.float32))
+            frames.append((depth, color, self.video.get_pose(f["video_idx"], "cpu")))
+        ren = self.renderer
+        vertices, colors, faces, _ = fuse_frames(frames, (ren.fx, ren.fy, ren.cx, ren.cy), self.device, **kwargs)
+        if output is not None:
+            save_mesh(output, vertices, colors, faces, mesh_name_suffix, scene)
+        return vertices, colors, faces
+
 
 # ---- the synthetic 640x480 stream of the config-3 test and of bench.py's `sequence` entry --------------------------------
 def synthetic_cfg(device, buffer, H=480, W=640):

@@ -910,6 +910,68 @@ int glorie_frame_reduce(const float* color_a, const float* color_b, int H, int W
 int glorie_mask_apply(const unsigned char* mask, int H, int W, const float* depth, const float* color_a,
                       const float* color_b, float* depth_out, float* color_a_out, float* color_b_out, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* TSDF fusion and mesh extraction                                                       */
+/* ------------------------------------------------------------------------------------ */
+
+/* A block-sparse truncated signed distance volume   reference: src/utils/generate_mesh.py:70-116, which drives
+ * Open3D's TSDF integration (RGB8 colour, depth_trunc 30) and its mesh extraction; the rules below restate the update
+ * because Open3D is not part of this project (parity with Open3D itself is not pinned).
+ *
+ * The volume, owned by the caller: `origin` (3 floats, HOST memory), voxel_length and `blocks_per_axis` (3 ints nbx, nby,
+ * nbz, HOST memory) span a grid of blocks of 8 x 8 x 8 voxels; voxel (i,j,k) samples origin + (i+0.5, j+0.5, k+0.5) *
+ * voxel_length.  table int32 [nbz,nby,nbx] holds -1 or a block id (all -1 at the start); block_index int32 [max_blocks]
+ * the table index of every block; the pool tsdf f32 [max_blocks,512], weight f32 [max_blocks,512], rgb f32
+ * [max_blocks,512,3] (0..255), voxel x fastest inside a block, zero at the start; counters int32 [8], zero at the start:
+ * [0] blocks in use, [1] pixels outside the bound (cumulative), [2] 1 when the last frame was refused, [3] blocks that
+ * passed the culling of the last integration, [4] new blocks the last frame asked for.
+ * Cameras are OpenCV pinholes; c2w f32 [4,4] on the device is a RIGID camera-to-world matrix (w2c = [R^T | -R^T t]).
+ *
+ * glorie_tsdf_allocate: every pixel with 0 < depth <= depth_trunc is back-projected to p; every block that overlaps the
+ * box [p - sdf_trunc, p + sdf_trunc] is flagged; a pixel whose box leaves the grid is counted in counters[1] and flags
+ * nothing.  Flagged blocks without an id get consecutive ids in ascending table index.  A frame that needs more than
+ * the max_blocks - counters[0] free blocks allocates nothing: GLORIE_ENOMEM, table and counters[0] unchanged.
+ * *n_blocks_out (HOST) = counters[0] afterwards.  Four launches and one 12-byte read-back (synchronises the stream).
+ * workspace: glorie_tsdf_allocate_workspace(nbx nby nbz) bytes. */
+size_t glorie_tsdf_allocate_workspace(long n_table);
+int glorie_tsdf_allocate(const float* depth, int H, int W, const float* c2w, float fx, float fy, float cx, float cy,
+                         float depth_trunc, float sdf_trunc, const float* origin, float voxel_length,
+                         const int* blocks_per_axis, int* table, int* block_index, int max_blocks, int* counters,
+                         void* workspace, int* n_blocks_out, void* stream);
+/* glorie_tsdf_integrate: one frame (depth f32 [H,W], color f32 [H,W,3] in [0,1]) into the first n_blocks blocks.  Blocks
+ * whose bounding sphere misses the frustum or the range (0, depth_trunc + sdf_trunc) are skipped (conservative).  Every
+ * other voxel X, all in fp32: p = R^T (X - t); skip if p.z <= 0; u_f = fx p.x / p.z + cx + 0.5, v_f alike; skip unless
+ * 1e-4 <= u_f < W - 1e-4 and 1e-4 <= v_f < H - 1e-4; u = (int)u_f, v = (int)v_f, d = depth[v,u]; skip if d <= 0 or
+ * d > depth_trunc; sdf = (d - p.z) sqrt(1 + ((u - cx)/fx)^2 + ((v - cy)/fy)^2); skip if sdf <= -sdf_trunc;
+ * new = min(1, sdf / sdf_trunc); tsdf = (tsdf w + new) / (w + 1), every colour channel alike with
+ * c = floor(clamp(color, 0, 1) 255); w += 1.  One thread owns one voxel: one launch, no atomics on the volume, bitwise
+ * repeatable.  No host synchronisation. */
+int glorie_tsdf_integrate(const float* depth, const float* color, int H, int W, const float* c2w, float fx, float fy,
+                          float cx, float cy, float depth_trunc, float sdf_trunc, const float* origin,
+                          float voxel_length, const int* blocks_per_axis, const int* block_index, int n_blocks,
+                          float* tsdf, float* weight, float* rgb, int* counters, void* stream);
+/* Mesh extraction: marching tetrahedra on the Kuhn split of every cell.  The cell of voxel (i,j,k) has corners
+ * (i+dx, j+dy, k+dz), corner index c = dx + 2 dy + 4 dz; its six tetrahedra are (0, a, a|b, 7) for the orders (a, b, c) of
+ * the axis bits (1,2,4), (1,4,2), (2,1,4), (2,4,1), (4,1,2), (4,2,1).  A cell is valid when all 8 corners are allocated
+ * with weight > 0; a corner is inside when tsdf < 0.  A cell owns the 7 edges from its corner 0 to corners 1, 2, 4, 3, 5,
+ * 6, 7 (the slots); an owned edge that changes sign and belongs to a valid cell carries one vertex at pa + t (pb - pa),
+ * t = ta / (ta - tb), a = the owner's corner 0 (evaluated in fp64 from the fp32 voxels and the fp64 origin and
+ * voxel_length, rounded once), colour likewise / 255.  A tetrahedron with 1 or 3 inside corners gives 1 triangle, with
+ * 2 two; the right-hand normal points towards increasing tsdf.  vertices f32 [V,3], colors f32 [V,3], faces int32 [F,3];
+ * vertices ordered by (block table index, cell index x fastest, slot), faces by (block table index, cell, tetrahedron,
+ * triangle): independent of the allocation order.
+ * glorie_tsdf_extract_count fills the workspace and returns counts_out[0..1] = V, F (HOST; synchronises the stream);
+ * glorie_tsdf_extract_emit then writes the outputs, sized by the caller, from the same workspace
+ * (glorie_tsdf_extract_workspace(nbx nby nbz, n_blocks) bytes) and the unchanged volume.  origin / voxel_length of
+ * _emit are doubles (HOST). */
+size_t glorie_tsdf_extract_workspace(long n_table, int n_blocks);
+int glorie_tsdf_extract_count(const float* origin, float voxel_length, const int* blocks_per_axis, const int* table,
+                              int n_blocks, const float* tsdf, const float* weight, void* workspace, int* counts_out,
+                              void* stream);
+int glorie_tsdf_extract_emit(const double* origin, double voxel_length, const int* blocks_per_axis, const int* table,
+                             int n_blocks, const float* tsdf, const float* weight, const float* rgb, void* workspace,
+                             float* vertices, float* colors, int* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
