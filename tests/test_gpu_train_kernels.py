@@ -76,12 +76,15 @@ class Case:
     pass
 
 
-def make_case(R, S, Np, seed, coef=None):
+def make_case(R, S, Np, seed, coef=None, unnormalised=False):
     """R rays x S samples on a cloud of Np points; every neighbour pattern is dealt round-robin over a random permutation of
     the samples, so each appears as soon as Q allows:
       full 8 neighbours | 2..7 valid, the rest I = -1, w = 0 | has == 0 with w and I left in place | duplicate indices
     plus (R >= 2) one ray all of whose samples have has == 0, and (Q >= 2) one zero-length view vector.  Row 0 of the cloud
-    is referenced only through the clamped -1 entries."""
+    is referenced only through the clamped -1 entries.
+    unnormalised (the inference tests): the same case - no draw of it changes - in which Q // 9 of the rows with has == 1 then
+    get all eight weights zero and as many get their weights halved (sum 0.5); `c.wsum` names them (0: untouched, 1: zero,
+    2: half) and `c.kind` the pattern each row was dealt."""
     c = Case()
     g = torch.Generator().manual_seed(seed)
     Q = R * S
@@ -123,6 +126,17 @@ def make_case(R, S, Np, seed, coef=None):
     # differ by their summation order alone by more than either differs from float64)
     c.cd = torch.randn(R, generator=g).abs() + 0.5
     c.cc = torch.randn(R, 3, generator=g).abs() + 0.5
+    c.kind, c.wsum = kind, torch.zeros(Q, dtype=torch.int64)
+    if unnormalised:
+        g2 = torch.Generator().manual_seed(seed + 7919)          # a stream of its own: the draws above stay what they were
+        live = torch.nonzero(has).flatten()
+        live = live[torch.randperm(live.numel(), generator=g2)]
+        n = Q // 9
+        c.wsum[live[:n]] = 1
+        c.wsum[live[n:2 * n]] = 2
+        w = c.w
+        w[c.wsum == 1] = 0.0
+        w[c.wsum == 2] *= 0.5
     used = torch.zeros(Np, dtype=torch.bool)
     ref = has[:, None] & (w != 0) & (I >= 0)
     used[I[ref]] = True
@@ -203,8 +217,8 @@ def _run_hip(c, P, color, gpu):
 
 
 class Ratios:
-    def __init__(self, label, frobenius):
-        self.label, self.frob, self.rows, self.bad = label, frobenius, [], []
+    def __init__(self, label, frobenius, m=None):
+        self.label, self.frob, self.rows, self.bad, self.m = label, frobenius, [], [], (M if m is None else float(m))
 
     def check(self, name, hip, r64, r32):
         """e_hip <= M max(e_f32, floor) over every element of the tensor; an identically zero reference must be met exactly"""
@@ -226,8 +240,8 @@ class Ratios:
         ratio = e_hip / max(e_f32, floor)
         self.rows.append((ratio, name))
         print(f"RATIO {self.label} {name} e_hip {e_hip:.3e} e_f32 {e_f32:.3e} floor {floor:.3e} ratio {ratio:.3f}")
-        if not e_hip <= M * max(e_f32, floor):
-            self.bad.append(f"{name}: e_hip {e_hip:.3e} > {M} * max(e_f32 {e_f32:.3e}, floor {floor:.3e})")
+        if not e_hip <= self.m * max(e_f32, floor):
+            self.bad.append(f"{name}: e_hip {e_hip:.3e} > {self.m} * max(e_f32 {e_f32:.3e}, floor {floor:.3e})")
 
     def finish(self):
         if self.rows:
