@@ -138,6 +138,20 @@ SIGNATURES = {
     "glorie_tsdf_extract_workspace": (_sz, [ctypes.c_long, _c_int]),
     "glorie_tsdf_extract_count": (_c_int, [_vp, _c_f, _vp, _vp, _c_int, _vp, _vp, _vp, ctypes.POINTER(_c_int), _vp]),
     "glorie_tsdf_extract_emit": (_c_int, [_vp, ctypes.c_double, _vp, _vp, _c_int] + [_vp] * 8),
+    "glorie_mesh_area_cdf_workspace": (_sz, [_c_int]),
+    "glorie_mesh_area_cdf": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, ctypes.POINTER(ctypes.c_double), _vp]),
+    "glorie_mesh_sample": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _c_int, _vp, _vp, _vp]),
+    "glorie_transform_points": (_c_int, [_vp, _vp, _c_int, _vp, _vp]),
+    "glorie_icp_moments_workspace": (_sz, [_c_int]),
+    "glorie_icp_moments": (_c_int, [_vp, _c_int, _vp, _c_int, _vp, _vp, _c_f, _vp, _vp, _vp]),
+    "glorie_nn_stats_workspace": (_sz, [_c_int]),
+    "glorie_nn_stats": (_c_int, [_vp, _c_int, _c_f, _vp, _vp, _vp]),
+    "glorie_mesh_depth_workspace": (_sz, [_c_int]),
+    "glorie_mesh_depth": (_c_int, [_vp, _c_int, _vp, _c_int, _vp] + [_c_f] * 4 + [_c_int, _c_int, _c_f, _c_f, _c_int]
+                          + [_vp] * 4),
+    "glorie_points_in_view": (_c_int, [_vp, _c_int, _vp] + [_c_f] * 4 + [_c_int, _c_int, _c_f, _vp, _vp]),
+    "glorie_depth_l1_workspace": (_sz, [_c_int, _c_int]),
+    "glorie_depth_l1_accumulate": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp]),
 }
 
 _lib = None

@@ -630,6 +630,16 @@ class SequenceRunner:
             save_mesh(output, vertices, colors, faces, mesh_name_suffix, scene)
         return vertices, colors, faces
 
+    # ---- eval_recon.py:229-248 ------------------------------------------------------------------------------------------
+    def recon(self, gt_vertices, gt_faces, output=None, mesh_kwargs=None, **kwargs):
+        """the reconstruction scores of the run (eval_recon.eval_recon): the mesh of mesh(output=output, **mesh_kwargs)
+        against the ground-truth mesh (device tensors); kwargs: eval_2d, eval_3d, align, kwargs_3d, kwargs_2d.  -> the
+        dict of accuracy, completion, completion_ratio, precision, recall, f-score and depth l1; with `output` also
+        metrics_recon.txt next to the mesh folder.  Not part of run()"""
+        from .eval_recon import eval_recon
+        vertices, _, faces = self.mesh(output=output, **(mesh_kwargs or {}))
+        return eval_recon((vertices, faces), (gt_vertices, gt_faces), output=output, **kwargs)
+
 
 # ---- the synthetic 640x480 stream of the config-3 test and of bench.py's `sequence` entry --------------------------------
 def synthetic_cfg(device, buffer, H=480, W=640):

@@ -972,6 +972,76 @@ int glorie_tsdf_extract_emit(const double* origin, double voxel_length, const in
                              int n_blocks, const float* tsdf, const float* weight, const float* rgb, void* workspace,
                              float* vertices, float* colors, int* faces, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Mesh evaluation: surface sampling, ICP moments, 3D statistics and depth L1            */
+/* ------------------------------------------------------------------------------------ */
+
+/* The kernels of the reconstruction scores   reference: src/utils/eval_recon.py, which works on the host with trimesh,
+ * Open3D, scipy's KD-tree and an off-screen OpenGL window; the rules below restate the steps because none of those
+ * belong to this project (parity with trimesh, Open3D and evaluate_3d_reconstruction is not pinned).
+ * A mesh is vertices f32 [V,3] and faces int32 [F,3] on the device.  A face with an index outside [0, V) is never read
+ * through: it has area 0, is not sampled and not drawn.  Cameras are OpenCV pinholes; w2c f32 [4,4] on the device is the
+ * world-to-camera matrix and pixel (u, v) samples image coordinates (u, v), the convention of the TSDF volume.
+ *
+ * glorie_mesh_area_cdf: cdf f64 [F] = the inclusive prefix sum of the triangle areas 0.5 |(p1 - p0) x (p2 - p0)|, in fp64
+ * from the fp32 vertices; *total_out (HOST) = cdf[F-1].  A face index outside [0, V) is GLORIE_EINVAL (a device flag read
+ * with the total: one 16-byte read-back, synchronises the stream).  Three launches, a fixed summation order.
+ * workspace: glorie_mesh_area_cdf_workspace(F) bytes. */
+size_t glorie_mesh_area_cdf_workspace(int F);
+int glorie_mesh_area_cdf(const float* vertices, int V, const int* faces, int F, double* cdf, void* workspace,
+                         double* total_out, void* stream);
+/* trimesh.sample.sample_surface   reference: src/utils/eval_recon.py:107-110
+ * u f32 [n,3] uniforms in [0,1) from the caller (there is no RNG in the kernel).  Sample i: face = the first f with
+ * cdf[f] > u[i,0] * cdf[F-1] (binary search in fp64; a face without area is never chosen); (a, b) = (u[i,1], u[i,2]), and
+ * (1 - a, 1 - b) when a + b > 1; points[i] = p0 + a (p1 - p0) + b (p2 - p0) in fp64, rounded once; face_of int32 [n].
+ * The caller rejects cdf[F-1] == 0.  One launch, no host synchronisation. */
+int glorie_mesh_sample(const float* vertices, int V, const int* faces, int F, const double* cdf, const float* u, int n,
+                       float* points, int* face_of, void* stream);
+/* out[i] = R in[i] + t with T = [R t; 0 0 0 1] f64 [4,4] row-major in HOST memory; fp64 arithmetic, one rounding. */
+int glorie_transform_points(const double* T, const float* in, int n, float* out, void* stream);
+/* The sums of one point-to-point ICP step   reference: src/utils/eval_recon.py:46-60 (Open3D registration_icp,
+ * TransformationEstimationPointToPoint)
+ * src f32 [n,3] (already transformed), tgt f32 [m,3], I int64 [n] and D f32 [n] from glorie_knn_query(k = 1).  Over the
+ * rows with 0 <= I < m and D < max_d2 (compared in fp32): out f64 [17] = {count, sum p [3], sum q [3], sum p q^T [9]
+ * row-major, sum |p - q|^2} with p = src[i], q = tgt[I[i]], every term formed in fp64 from the fp32 points.  Two
+ * launches, a fixed summation order, no host synchronisation.  workspace: glorie_icp_moments_workspace(n) bytes. */
+size_t glorie_icp_moments_workspace(int n);
+int glorie_icp_moments(const float* src, int n, const float* tgt, int m, const int64_t* I, const float* D, float max_d2,
+                       void* workspace, double* out, void* stream);
+/* accuracy / completion / completion_ratio   reference: src/utils/eval_recon.py:25-43
+ * D f32 [Q] squared nearest-neighbour distances -> out f64 [3] = {sum sqrt((double)D), #{sqrt((double)D) <
+ * (double)threshold}, sum (double)D}; Q = 0 gives zeros.  Two launches, a fixed summation order, no host
+ * synchronisation.  workspace: glorie_nn_stats_workspace(Q) bytes. */
+size_t glorie_nn_stats_workspace(int Q);
+int glorie_nn_stats(const float* D, int Q, float threshold, void* workspace, double* out, void* stream);
+/* The depth map of a mesh   reference: src/utils/eval_recon.py:166-217 (Open3D's off-screen visualiser with
+ * mesh_show_back_face and a constant z_far)
+ * Both sides of a triangle are drawn.  A pixel is covered by a triangle when its ray meets the triangle, edges
+ * included; its depth is the smallest camera-frame z of those intersections with z_near < z <= z_far (fp64 from the fp32
+ * inputs, rounded once), 0 where there is none.  A triangle that crosses the plane z = z_near keeps the part in front of
+ * it, as clipping it into one or two triangles would.  depth f32 [H,W]; depth_bits u32 [H,W] scratch.  z_near > 0.
+ * policy 0: a triangle whose pixel box exceeds 256 pixels is spread over workgroups by a second launch, the others are
+ * walked by one lane each; 1: every triangle by one lane; 2: every triangle by workgroups - the same bits in all three.
+ * atomicMin on the bits of the positive depth: independent of arrival order, bitwise repeatable.  Four launches, no host
+ * synchronisation.  workspace: glorie_mesh_depth_workspace(F) bytes. */
+size_t glorie_mesh_depth_workspace(int F);
+int glorie_mesh_depth(const float* vertices, int V, const int* faces, int F, const float* w2c, float fx, float fy, float cx,
+                      float cy, int H, int W, float z_near, float z_far, int policy, void* workspace,
+                      unsigned* depth_bits, float* depth, void* stream);
+/* check_proj   reference: src/utils/eval_recon.py:63-92
+ * count int32 [1] = the points f32 [n,3] with z > 0, edge < u < W - edge and edge < v < H - edge (fp64 from the fp32
+ * inputs).  One count per wave, one integer atomic per workgroup.  No host synchronisation. */
+int glorie_points_in_view(const float* points, int n, const float* w2c, float fx, float fy, float cx, float cy, int H,
+                          int W, float edge, int* count, void* stream);
+/* The depth L1 of one view   reference: src/utils/eval_recon.py:219-224
+ * err f64 [n_views], valid int32 [n_views]: err[view] = mean |gt_depth - rec_depth| over the pixels with rec_depth > 0,
+ * valid[view] = the number of such pixels (0: the view is skipped, err[view] = 0).  A thousand views cost one read-back
+ * at the end.  Two launches, a fixed summation order, no host synchronisation.
+ * workspace: glorie_depth_l1_workspace(H, W) bytes. */
+size_t glorie_depth_l1_workspace(int H, int W);
+int glorie_depth_l1_accumulate(const float* gt_depth, const float* rec_depth, int H, int W, void* workspace, double* err,
+                               int* valid, int view, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
