@@ -111,3 +111,26 @@ def random_select(l, k, generator=None):
     if l <= 0 or k <= 0:
         return []
     return torch.randperm(int(l), generator=generator)[:min(int(l), int(k))].tolist()
+
+
+def final_refine_window(mapped, skipped, counter, map_rays, generator=None, pix_warping=None):
+    """the window of one pass of Mapper.final_refine (mapper.py:816-836 through optimize_map, :541-584): the 'global'
+    method with mapping_window_size = counter - 1.  Host only.
+    mapped: keyframes [0, mapped) have been through the mapper, `skipped` of them were not mapped; counter: the video's
+    keyframe count.  The candidates are the mapped keyframes without the last one, L (keyframe_dict[:-1]);
+    random_select draws max(counter - 3, 0) of them; window = selected + [L].  per = map_rays // (len(window) + 1) pixels
+    of every window frame: the reference counts the current frame, which colour refinement then leaves out (:575, :584);
+    at least 1 (the reference would sample none).  pix_warping=True with a window beyond the pixel-warping kernel's
+    frame limit is an error (raised before anything is drawn).  -> (window, per)"""
+    from .warp_loss import MAX_FRAMES
+    skipped = set(int(f) for f in skipped)
+    frames = [f for f in range(int(mapped)) if f not in skipped]
+    if not frames:
+        raise ValueError("final refinement needs at least one mapped keyframe")
+    cand, last = frames[:-1], frames[-1]
+    num = max(int(counter) - 3, 0)
+    size = min(len(cand), num) + 1
+    if pix_warping is True and size > MAX_FRAMES:
+        raise ValueError(f"pix_warping supports up to {MAX_FRAMES} window frames, the refinement window has {size}")
+    window = [cand[s] for s in random_select(len(cand), num, generator)] + [last]
+    return window, max(1, int(map_rays) // (len(window) + 1))

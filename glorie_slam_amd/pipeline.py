@@ -20,11 +20,13 @@ from .color_grad import (COLOR_GRAD_THRESHOLD, RADIUS_ADD_MAX, RADIUS_ADD_MIN, R
                          get_samples_with_pixel_grad)
 from .common import get_rays_from_uv
 from .frontend import Frontend
-from .keyframe_select import frustum_feature_mask, keyframe_selection_overlap, random_select
+from .keyframe_select import final_refine_window, frustum_feature_mask, keyframe_selection_overlap, random_select
 from .motion_filter import MotionFilter
 from .neural_point import deform_points, proxy_render_depth, se3_inv, update_points_pos
 from .render_train import FeatureAdam
+from .warp_loss import MAX_FRAMES as MAX_WARP_FRAMES
 from .warp_loss import FrameTable, pix_warping_loss
+from .window_rays import WindowTable, window_rays
 
 
 class _CfgVideo:
@@ -143,6 +145,8 @@ class SequenceRunner:
         self.deform_stats = {"calls": 0, "dirty_keyframes": 0, "points_moved": 0}
         self._deform_counts = None            # device int64 [dirty keyframes, points moved], read once per keyframe
         self._render_views = None             # inside map_keyframe with render_depth: frame -> (depth, c2w) or None
+        self.refine_losses = []               # final_refine: (first, last) loss per outer pass
+        self.refine_windows = []              # final_refine: the window of every outer pass (keyframe ids)
 
     # ---- tracker.py:33-77 ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -250,6 +254,27 @@ class SequenceRunner:
             self._render_views = None
             self._read_deform_stats()
 
+    def _mapping_loss(self, ro, rd, d, gt_col, radius, geo, col_f, warp=None):
+        """the loss of one mapping iteration (mapper.py:497-507) on the feature tables geo / col_f: depth and colour L1
+        over the rays that carry a depth and met the cloud, plus the pixel-warping term of the window `warp` (its value is
+        left in warp["value"]), per seen ray -> (loss, rendered depth, rendered colour, seen [N] as float)"""
+        npc, ren = self.npc, self.renderer
+        depth, _, colour, _, counts = ren.render_batch_ray(npc, self.decoders, rd, ro, self.device, "color", gt_depth=d,
+                                                           npc_geo_feats=geo, npc_col_feats=col_f,
+                                                           cloud_pos=npc.cloud_pos(), dynamic_r_query=radius)
+        # (masked sums instead of `x[seen].sum()`: boolean indexing sizes its result on the host - one device round trip
+        # in the forward and one in the backward pass of every iteration)
+        seen = ((counts > 0) & (d > 0)).to(depth.dtype)
+        loss = (torch.abs(d - depth) * seen).sum() + 0.5 * (torch.abs(gt_col - colour) * seen[:, None]).sum()
+        if warp is not None:
+            # inside the numerator: its weight relative to the L1 sums is the reference's (mapper.py:497-507)
+            w = pix_warping_loss(ro, rd, depth, warp["c2ws"], ren.fx, ren.fy, ren.cx, ren.cy, self.video.wd,
+                                 self.video.ht, warp["frame_ids"], warp["ray_frame"], warp["table"], gt_col,
+                                 nan_to_zero=True)
+            loss = loss + self.w_pix_warp_loss * w
+            warp["value"].copy_(w.detach())
+        return loss / seen.sum().clamp_min(1), depth, colour, seen
+
     def _optimize_keyframe(self, k, rmaps):
         """the mapping iterations of map_keyframe (after the insertion)"""
         npc, dec, ren = self.npc, self.decoders, self.renderer
@@ -307,21 +332,7 @@ class SequenceRunner:
                 else:
                     ro, rd, d, gt_col, radius = self._window_rays(win, pix, rq)
             opt.zero_grad()
-            depth, _, colour, _, counts = ren.render_batch_ray(npc, dec, rd, ro, self.device, "color", gt_depth=d,
-                                                               npc_geo_feats=geo, npc_col_feats=col_f,
-                                                               cloud_pos=npc.cloud_pos(), dynamic_r_query=radius)
-            # (masked sums instead of `x[seen].sum()`: boolean indexing sizes its result on the host - one device round trip
-            # in the forward and one in the backward pass of every iteration)
-            seen = ((counts > 0) & (d > 0)).to(depth.dtype)
-            loss = (torch.abs(d - depth) * seen).sum() + 0.5 * (torch.abs(gt_col - colour) * seen[:, None]).sum()
-            if warp is not None:
-                # inside the numerator: its weight relative to the L1 sums is the reference's (mapper.py:497-507)
-                w = pix_warping_loss(ro, rd, depth, warp["c2ws"], ren.fx, ren.fy, ren.cx, ren.cy, self.video.wd,
-                                     self.video.ht, warp["frame_ids"], warp["ray_frame"], warp["table"], gt_col,
-                                     nan_to_zero=True)
-                loss = loss + self.w_pix_warp_loss * w
-                warp["value"].copy_(w.detach())
-            loss = loss / seen.sum().clamp_min(1)
+            loss, depth, colour, seen = self._mapping_loss(ro, rd, d, gt_col, radius, geo, col_f, warp)
             if self.map_probe is not None and not torch.cuda.is_current_stream_capturing():
                 self.map_probe(k, dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(), colour=colour.detach(),
                                        seen=seen, loss=loss.detach(), warp=warp, window=win,
@@ -584,9 +595,142 @@ class SequenceRunner:
             self.map_keyframe(self.mapped)
             self.mapped += 1
 
+    # ---- mapper.py:816-855 ------------------------------------------------------------------------------------------
+    def final_refine(self, outer_iters=5, iters=None, pix_warping=None, save_final_pcl=False, output=None):
+        """Mapper.final_refine: after the last global BA the point features are trained once more over all keyframes
+        (mapping_keyframe with color_refine=True: the cloud is deformed, no point is inserted, the decoders are frozen,
+        no frustum selection).  `outer_iters` passes; each selects its window (keyframe_select.final_refine_window:
+        the 'global' method over every mapped keyframe), recomputes its views and radius maps, and runs 2 * map_iters
+        iterations (`iters` when given) with a fresh FeatureAdam on the two feature tables.  An iteration's rays come
+        from one launch (window_rays.py) whatever the window's size, its loss is map_keyframe's (_mapping_loss), in the
+        colour stage at the runner's learning rate throughout.  pix_warping: None is the runner's setting while the
+        window fits the pixel-warping kernel (warp_loss.MAX_FRAMES frames), off beyond; True beyond it is an error.
+        Runs eagerly.  save_final_pcl with `output`: final_point_cloud.npy, npc_cloud.npy and final_point_cloud.ply
+        there (mapper.py:838-849).  The passes' (first, last) losses go to refine_losses, their windows to
+        refine_windows; the bookkeeping of map_keyframe is not touched.
+        -> dict(window_sizes, per, losses, pix_warping, ms_per_iter)"""
+        npc, dec, ren, v = self.npc, self.decoders, self.renderer, self.video
+        n_it = 2 * self.map_iters if iters is None else int(iters)
+        self.refine_losses, self.refine_windows = [], []
+        sizes, pers, warped, elapsed, steps = [], [], [], 0.0, 0
+        frozen = [(p, p.requires_grad) for p in dec.parameters()]
+        # the first window before anything runs on the GPU: an empty map or an impossible pix_warping ends the call here
+        first_window = final_refine_window(self.mapped, self.skipped, int(v.counter.value), self.map_rays, self.gen,
+                                           pix_warping=pix_warping)
+        if npc.pts_num() == 0:
+            raise ValueError("final refinement needs a point cloud")
+        self._render_views = None
+        try:
+            if self.bind_npc_with_pose:
+                with torch.no_grad():
+                    self._deform()
+            for p, _ in frozen:                    # fix_geo_decoder and fix_color_decoder: no decoder gradient is formed
+                p.requires_grad_(False)
+            dec.train()
+            for o in range(int(outer_iters)):
+                window, per = first_window if o == 0 else final_refine_window(
+                    self.mapped, self.skipped, int(v.counter.value), self.map_rays, self.gen, pix_warping=pix_warping)
+                with torch.no_grad():
+                    if self.render_depth is not None:
+                        self._render_views = {}
+                        views = {f: self._render_view(f) for f in window}
+                        window = [f for f in window if views[f] is not None]     # (per stays, mapper.py:564, :584)
+                        views = {f: views[f] for f in window}
+                    else:
+                        views = {f: self._keyframe_view(f) for f in window}
+                    if not window:
+                        raise ValueError("final refinement: every window frame was skipped")
+                    warp_on = (self.pix_warping if pix_warping is None else bool(pix_warping)) \
+                        and len(window) <= MAX_WARP_FRAMES
+                    rq = [self._radius_maps(f, views[f], add=False)[1] for f in window] if self.color_grad else None
+                    const_r = 0.5 * (npc.radius_add + npc.radius_query) if (rq is None and npc.use_dynamic_radius) else None
+                    c2ws = torch.stack([views[f][1] for f in window]).float().contiguous()
+                    table = WindowTable([views[f][0] for f in window], [self.images[f] for f in window], c2ws, rq,
+                                        channels_first=True)
+                    frame_ids = torch.tensor(window, dtype=torch.int64).to(self.device)
+                    win = {"window": window, "views": views, "per": per, "frame_ids": frame_ids, "table": table}
+                    warp = None
+                    if warp_on:
+                        warp = {"c2ws": table.c2ws, "frame_ids": frame_ids, "ray_frame": frame_ids.repeat_interleave(per),
+                                "table": FrameTable(table.images, channels_first=True),
+                                "value": torch.zeros((), device=self.device), "first": None}
+                    # every iteration's draw in one transfer: [iteration][ii | jj][frame-major rays]
+                    n_rays = per * len(window)
+                    draws = torch.stack([torch.randint(0, v.wd, (n_it, n_rays), generator=self.gen),
+                                         torch.randint(0, v.ht, (n_it, n_rays), generator=self.gen)], 1).to(self.device)
+                    all_depth = bool(torch.stack([(views[f][0] > 0).all() for f in window]).all())
+                geo = npc.geo_feats.detach().clone().requires_grad_(True)
+                col_f = npc.col_feats.detach().clone().requires_grad_(True)
+                opt = FeatureAdam([{"params": [geo], "lr": 0.005}, {"params": [col_f], "lr": 0.005}])
+                self.last_optimizer = opt
+                first = last = None
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ren.assume_depth = all_depth
+                try:
+                    for it in range(n_it):
+                        pix = draws[it]
+                        with torch.no_grad():
+                            ro, rd, d, gt_col, radius = window_rays(table, pix[0], pix[1], per, ren.fx, ren.fy, ren.cx,
+                                                                    ren.cy, const_radius=const_r)
+                        opt.zero_grad()
+                        loss, depth, colour, seen = self._mapping_loss(ro, rd, d, gt_col, radius, geo, col_f, warp)
+                        if self.map_probe is not None:
+                            self.map_probe(window[-1], dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(),
+                                                            colour=colour.detach(), seen=seen, loss=loss.detach(),
+                                                            warp=warp, window=win, frustum=None, radius=radius, pix=pix,
+                                                            refine=o))
+                        loss.backward()
+                        opt.step()
+                        last = loss.detach()
+                        if first is None:
+                            first = last
+                finally:
+                    ren.assume_depth = False
+                torch.cuda.synchronize()
+                elapsed += time.perf_counter() - t0
+                steps += n_it
+                with torch.no_grad():
+                    npc.update_geo_feats(geo.detach())
+                    npc.update_col_feats(col_f.detach())
+                nan = float("nan")
+                self.refine_losses.append((float(first), float(last)) if n_it else (nan, nan))
+                self.refine_windows.append(list(window))
+                sizes.append(len(window))
+                pers.append(per)
+                warped.append(warp is not None)
+        finally:
+            for p, req in frozen:
+                p.requires_grad_(req)
+            dec.eval()
+            self._render_views = None
+            self._read_deform_stats()
+        if save_final_pcl and output is not None:
+            self.save_final_pcl(output)
+        return {"window_sizes": sizes, "per": pers[0] if pers else first_window[1], "losses": list(self.refine_losses),
+                "pix_warping": bool(warped) and all(warped), "ms_per_iter": 1e3 * elapsed / max(steps, 1)}
+
+    def save_final_pcl(self, output):
+        """final_point_cloud.npy ([n,6]: input_pos | input_rgb), npc_cloud.npy ([n,3]: cloud_pos) and
+        final_point_cloud.ply (the input points, colours input_rgb / 255: add_neural_points stores 0..255 as the
+        reference does) under `output` (mapper.py:838-849)"""
+        import os
+
+        import numpy as np
+
+        from .generate_mesh import write_ply
+        os.makedirs(str(output), exist_ok=True)
+        pos = self.npc.input_pos().detach().cpu().numpy()
+        rgb = self.npc.input_rgb().detach().cpu().numpy()
+        np.save(os.path.join(str(output), "final_point_cloud"), np.hstack((pos, rgb)))
+        np.save(os.path.join(str(output), "npc_cloud"), self.npc.cloud_pos().detach().cpu().numpy())
+        write_ply(os.path.join(str(output), "final_point_cloud.ply"), pos, np.zeros((0, 3), np.int32),
+                  rgb.astype(np.float64) / 255.0)
+
     # ---- the stream -------------------------------------------------------------------------------------------------
-    def run(self, frames, intrinsics, final_ba_steps=7):
-        """frames: iterable of (tstamp, image [1,3,H,W] in [0,1]).  Returns a summary dict."""
+    def run(self, frames, intrinsics, final_ba_steps=7, final_refine=False):
+        """frames: iterable of (tstamp, image [1,3,H,W] in [0,1]).  final_refine: the final refinement of the map
+        (final_refine() with its defaults) after the final BA.  Returns a summary dict."""
         for tstamp, image in frames:
             self.track(tstamp, image, intrinsics)
             self.map_pending()
@@ -597,6 +741,8 @@ class SequenceRunner:
             with torch.no_grad():                                           # the cloud follows the final trajectory
                 self._deform()
             self._read_deform_stats()
+        if final_refine:
+            self.final_refine()
         torch.cuda.synchronize()
         return {"keyframes": int(self.video.counter.value), "final_ba_edges": int(n_edges), "mapped": self.mapped,
                 "points": int(self.npc.pts_num()), "losses": list(self.losses), "timing": self.timing}

@@ -1042,6 +1042,28 @@ size_t glorie_depth_l1_workspace(int H, int W);
 int glorie_depth_l1_accumulate(const float* gt_depth, const float* rec_depth, int H, int W, void* workspace, double* err,
                                int* valid, int view, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Ray gather of a window of keyframes (the final refinement)                            */
+/* ------------------------------------------------------------------------------------ */
+
+/* The rays, depths, colours and radii of one training iteration over M keyframes
+ *   reference: src/mapper.py:437-466 (get_samples per window frame), src/utils/common.py:39-54 (get_rays_from_uv)
+ * depth_table, image_table, radius_table: DEVICE arrays of M `const float*` - depth maps [H,W] f32, images [3,H,W] f32
+ * (chw = 1) or [H,W,3] (chw = 0), radius maps [H,W] f32 (radius_table may be NULL).  c2ws [M,16] f32 row-major, the
+ * renderer's OpenGL convention.  ii, jj [N] int64 with N = M * per, frame-major: ray r belongs to window slot r / per and
+ * reads pixel column ii[r], row jj[r].  There is no limit on M.
+ * Outputs for ray r of slot m at (i, j): rays_o [N,3] = c2w_m[:3,3];  rays_d [N,3] with dx = (float(i) - cx) / fx,
+ * dy = -((float(j) - cy) / fy), dz = -1: rays_d[a] = (dx R[a][0] + dy R[a][1]) + dz R[a][2], every division, product and
+ * sum rounded to fp32 on its own (no fused multiply-add);  depth [N] = depth_m[j,i];  color [N,3] = image_m[:, j, i];
+ * radius [N] = radius_m[j,i], or const_radius without a radius_table; want_radius = 0: radius is not written (may be NULL).
+ * The draw is trusted to lie inside the image and is not checked on the host; the kernel clamps i to [0, W-1] and j to
+ * [0, H-1] before it forms the direction and the addresses, so a bad draw cannot read outside a map.
+ * N = 0 launches nothing.  One launch, no atomics, no host synchronisation, no output sized by the data. */
+int glorie_window_rays(const void* depth_table, const void* image_table, const void* radius_table, const float* c2ws, int M,
+                       int per, int chw, int H, int W, float fx, float fy, float cx, float cy, const int64_t* ii,
+                       const int64_t* jj, float const_radius, int want_radius, float* rays_o, float* rays_d, float* depth,
+                       float* color, float* radius, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
