@@ -99,6 +99,7 @@ __global__ __launch_bounds__(256) void flow_conv7_kernel(const float* __restrict
 //    a pixel cover 64 contiguous bytes with each; the stores are unconditional buffer stores (pixels past the end are
 //    dropped by the range check) so that the compiler can count them instead of waiting for vmcnt(0).
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2_;
 constexpr int kFlowPadY = 3, kFlowPadL = 3, kFlowPadW = 8;     // rows above/below, pixels left, extra pixels per row
 
 __global__ __launch_bounds__(256, 2) void flow_conv7_padded_kernel(const _Float16* __restrict__ fp,
@@ -213,6 +214,239 @@ __global__ __launch_bounds__(256) void flow_pad_kernel(const float4* __restrict_
   *reinterpret_cast<f16x4*>(padded + (((n * (H + 2 * kFlowPadY) + y + kFlowPadY) * (W + kFlowPadW)) + x + kFlowPadL) * 4) = h;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The whole flow encoder as one launch: relu(conv3x3(relu(conv7x7(motion) + b7)) + b3), 4 -> 128 -> 64 channels.
+//
+// A workgroup owns an 8 x 16 pixel tile of one map.
+// Stage 1 evaluates the 7x7 layer for the tile plus a one-pixel halo (10 x 18 = 180 hidden pixels, 12 MFMA pixel blocks of
+// which the last holds 4) with the arithmetic of flow_conv7_padded_kernel - same weight and pixel fragments, the seven K
+// slices in the same order, same bias / ReLU / fp16 rounding - and writes the 128 channels of every hidden pixel into LDS
+// instead of HBM (46 KB, [pixel][128] halfs, the 16-byte slot of a row XORed with the row's low four bits).  The 16 x 25
+// pixels of the padded motion map that the tile's stencils touch are staged in LDS once (3.3 KB); a wave owns 32 hidden
+// channels (14 weight fragments, loaded once per workgroup) and walks all 12 pixel blocks.  A hidden pixel OUTSIDE the map is
+// the 3x3 layer's zero padding, not a value of the 7x7 layer: it is written as zeros.
+// Stage 2 is the 3x3 layer of conv_igemm_kernel<EPI_BIAS_ACT, 4, 64, 4, 1, 2> on that tile: a wave owns 32 output channels
+// (two 16-row blocks of the paired weight layout) x 4 tile rows of 16 pixels; K runs 64-channel chunk outermost, the nine
+// taps inside, the two 32-wide slices of a chunk in order, so every accumulator sees the MFMA sequence of the two-launch
+// path and the output is bit-identical.  The pixel fragments are ds_read_b128 at the tap's row / column offset in the hidden
+// tile.  The weights of a K step (64 rows x 64 channels, 8 KB, the same for every workgroup: L2 resident) are loaded
+// ROW-contiguous - 8 lanes per 128-byte row segment, a quarter of the step per wave; a load in fragment order has every
+// lane on a cache line of its own and the kernel is bound by the tag look-ups: 74 us - kFeAhead K steps ahead into
+// registers, and pass through a double-buffered LDS tile that turns them into MFMA fragments: one barrier per K step.
+// (Each wave staging its own 32 rows in a private buffer needs no barrier but fetches every row twice: 52.6 us against
+// 49.1.)
+// What it saves against the two launches: the 44 MB hidden map written to and read back from HBM, the per-tap staging of the
+// pixel operand, one launch.  What it pays: the 7x7 layer is evaluated for 192 pixel slots per 128 outputs.
+constexpr int kFeTH = 8, kFeTW = 16;                                  // output tile
+constexpr int kFeHW = kFeTW + 2, kFeHH = kFeTH + 2;                   // hidden tile
+constexpr int kFeHP = kFeHW * kFeHH;                                  // 180 hidden pixels
+[[maybe_unused]] constexpr int kFeBlocks = (kFeHP + 15) / 16;                          // 12 MFMA pixel blocks
+constexpr int kFeC = 128, kFeNpad = 128, kFeNout = 64;                // hidden channels, packed rows per tap, outputs
+constexpr int kFePR = kFeHH + 6, kFePC = 26;                          // motion patch: 16 rows x 25 (+ 1) pixels of 4 halfs
+static_assert(kFePC >= kFeHW + 7 && kFePC % 2 == 0 && kFePR * (kFePC / 2) <= 256, "one 16-byte unit of the patch per thread");
+[[maybe_unused]] constexpr int kFePB = kFePR * kFePC * 8 + 128;                        // second copy: 32 banks away from the first
+[[maybe_unused]] constexpr int kFeAhead = 8;                          // K steps of stage-2 weights in flight (8 VGPRs each)
+[[maybe_unused]] constexpr int kFeSteps = 18;                         // 2 chunks of 64 channels x 9 taps
+
+__global__ __launch_bounds__(256, 2) void flow_encoder_kernel(const _Float16* __restrict__ fp, unsigned fp_bytes,
+                                                              const _Float16* __restrict__ w7,
+                                                              const float* __restrict__ b7,
+                                                              const _Float16* __restrict__ w3, unsigned w3_bytes,
+                                                              const float* __restrict__ b3, _Float16* __restrict__ out,
+                                                              unsigned out_bytes, int os, int H, int W, int tiles_x,
+                                                              int tiles_y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __shared__ __attribute__((aligned(16))) char hid[kFeHP * kFeC * 2];
+  // kFePR x kFePC pixels of 8 bytes, twice: at 0 as pairs (2u, 2u + 1), at kFePB as pairs (2u + 1, 2u + 2), so that the two
+  // pixels of any fragment are ONE aligned 16-byte unit (an 8-byte-aligned fragment is read as ds_read2_b64: 16 LDS cycles
+  // instead of 4); + 16 bytes that the threads without a unit write
+  __shared__ __attribute__((aligned(16))) char patch[kFePB + kFePR * kFePC * 8 + 128];
+  __shared__ __attribute__((aligned(16))) char wbuf[2][64 * 128];        // two K steps of weights: 64 rows x 64 channels each
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int col = lane & 15, kg = lane >> 4;
+  const int tx = blockIdx.x % tiles_x, trest = blockIdx.x / tiles_x;
+  const int ty = trest % tiles_y, n = trest / tiles_y;
+  const int y0 = ty * kFeTH, x0 = tx * kFeTW;
+  const int wm = wv & 1, wn = wv >> 1;
+
+  // the tile's patch of the padded motion map: patch row pr / pixel pc = padded row y0 - 1 + pr / pixel x0 - 1 + pc (the
+  // stencil rows of hidden row hy are patch rows hy .. hy + 6, the taps of hidden column hx and lane group kg are patch
+  // pixels hx + 2kg, hx + 2kg + 1).  One pass of 8-byte loads, issued ahead of the weight loads; a pixel outside the
+  // padded map (only hidden pixels outside the map read those) is refused by the descriptor's range check: zeros.
+  u32x2_ pv0, pv1, pv2;
+  const int punit = tid < kFePR * (kFePC / 2) ? tid * 16 : kFePR * kFePC * 8;     // (the gap behind either copy)
+  {
+    const __amdgpu_buffer_rsrc_t rF = __builtin_amdgcn_make_buffer_rsrc((void*)fp, 0, fp_bytes, 0x00020000);
+    const int WP = W + kFlowPadW, HP = H + 2 * kFlowPadY;
+    const int ppr = tid / (kFePC / 2), ppu = tid - ppr * (kFePC / 2);
+    const int prow = y0 - 1 + ppr, pcol = x0 - 1 + 2 * ppu;
+    const bool rok = ppr < kFePR && (unsigned)prow < (unsigned)HP;
+    const bool ok0 = rok && (unsigned)pcol < (unsigned)WP, ok1 = rok && (unsigned)(pcol + 1) < (unsigned)WP;
+    const bool ok2 = rok && (unsigned)(pcol + 2) < (unsigned)WP;
+    const int base = ((n * HP + prow) * WP + pcol) * 8;
+    pv0 = __builtin_amdgcn_raw_buffer_load_b64(rF, ok0 ? (unsigned)base : 0x80000000u, 0, 0);
+    pv1 = __builtin_amdgcn_raw_buffer_load_b64(rF, ok1 ? (unsigned)(base + 8) : 0x80000000u, 0, 0);
+    pv2 = __builtin_amdgcn_raw_buffer_load_b64(rF, ok2 ? (unsigned)(base + 16) : 0x80000000u, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  // stage-1 weights: the wave's hidden channels 32 wv .. 32 wv + 31; MFMA row `col` of block mi is channel
+  // 32 wv + 8 (col / 4) + 4 mi + col % 4, so that the lane ends up with the 8 consecutive channels 32 wv + 8 kg .. + 7
+  f16x8 wf[2][7];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi) {
+    const int ch = wv * 32 + (col >> 2) * 8 + mi * 4 + (col & 3);
+#pragma unroll
+    for (int ky = 0; ky < 7; ++ky)
+      wf[mi][ky] = *reinterpret_cast<const f16x8*>(w7 + (size_t)ch * kFlowK + ky * 32 + kg * 8);
+  }
+  float4 b[2];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi) b[mi] = *reinterpret_cast<const float4*>(b7 + wv * 32 + kg * 8 + mi * 4);
+  __builtin_amdgcn_sched_barrier(0);
+
+  // stage-2 weights of K step t (chunk t / 9, tap t % 9), 64 rows x 128 bytes: the wave fetches rows 16 wv + 8 i + lane / 8
+  // (i = 0, 1), 16-byte piece lane % 8.  The first kFeAhead steps are in flight during stage 1.
+  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)w3, 0, w3_bytes, 0x00020000);
+  const unsigned wvoff = (unsigned)(((wv * 16 + (lane >> 3)) * kFeC) * 2 + (lane & 7) * 16);
+  auto load_w = [&](int t, u32x4_ (&wr)[2]) {
+    const int ch = t / 9, d = t - ch * 9;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      wr[i] = __builtin_amdgcn_raw_buffer_load_b128(rW, wvoff, ((d * kFeNpad + i * 8) * kFeC + ch * 64) * 2, 0);
+  };
+  constexpr int D = kFeAhead, R = kFeAhead + 1;
+  u32x4_ wq[R][2];
+#pragma unroll
+  for (int t = 0; t < D; ++t) load_w(t, wq[t]);
+  __builtin_amdgcn_sched_barrier(0);
+
+  // ---- stage 1: the hidden tile ----
+  {
+    // (every thread stores - the threads past the patch write zeros behind it: no branch for the loads to sink into)
+    *reinterpret_cast<u32x4_*>(patch + punit) = u32x4_{pv0[0], pv0[1], pv1[0], pv1[1]};
+    *reinterpret_cast<u32x4_*>(patch + kFePB + punit) = u32x4_{pv1[0], pv1[1], pv2[0], pv2[1]};
+    __syncthreads();
+    // hidden pixel hp = 16 blk + col sits at map pixel (y0 - 1 + hp / 18, x0 - 1 + hp % 18)
+    auto issue = [&](int blk, u32x4_ (&r)[7]) {
+      const int hp = min(blk * 16 + col, kFeHP - 1), hy = hp / kFeHW, hx = hp - hy * kFeHW;
+      const int q = hx + 2 * kg;                       // first of the lane's two patch pixels: copy q & 1, unit q / 2
+      const u32x4_* src = reinterpret_cast<const u32x4_*>(patch) + (q & 1) * (kFePB / 16) + hy * (kFePC / 2) + (q >> 1);
+#pragma unroll
+      for (int ky = 0; ky < 7; ++ky) r[ky] = src[ky * (kFePC / 2)];
+    };
+    auto finish = [&](int blk, const u32x4_ (&r)[7]) {
+      f32x4 acc[2];
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) acc[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ky = 0; ky < 7; ++ky) {
+        const f16x8 xf = __builtin_bit_cast(f16x8, r[ky]);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) acc[mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[mi][ky], xf, acc[mi], 0, 0, 0);
+      }
+      const int hp = blk * 16 + col, hy = hp / kFeHW, hx = hp - hy * kFeHW;
+      const int y = y0 - 1 + hy, x = x0 - 1 + hx;
+      const bool in = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
+      f16x8 o;
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) {
+        o[mi * 4 + 0] = in ? (_Float16)fmaxf(acc[mi][0] + b[mi].x, 0.0f) : (_Float16)0.0f;
+        o[mi * 4 + 1] = in ? (_Float16)fmaxf(acc[mi][1] + b[mi].y, 0.0f) : (_Float16)0.0f;
+        o[mi * 4 + 2] = in ? (_Float16)fmaxf(acc[mi][2] + b[mi].z, 0.0f) : (_Float16)0.0f;
+        o[mi * 4 + 3] = in ? (_Float16)fmaxf(acc[mi][3] + b[mi].w, 0.0f) : (_Float16)0.0f;
+      }
+      if (hp < kFeHP)                                  // channels 32 wv + 8 kg .. + 7 of hidden pixel hp: slot 4 wv + kg
+        *reinterpret_cast<f16x8*>(hid + hp * (kFeC * 2) + (((wv * 4 + kg) ^ (hp & 15)) << 4)) = o;
+    };
+    u32x4_ r[2][7];
+    issue(0, r[0]);
+#pragma unroll
+    for (int i = 0; i < kFeBlocks; ++i) {
+      if (i + 1 < kFeBlocks) issue(i + 1, r[(i + 1) & 1]);
+      finish(i, r[i & 1]);
+    }
+  }
+
+  // ---- stage 2: 3x3 over the hidden tile.  Wave = 32 output channels (wm) x tile rows 4 wn .. 4 wn + 3 ----
+  // byte address of the lane's fragment (hidden row 4 wn + j, hidden column col + dx, logical slot kg); the slots of the
+  // other K slices differ in bits 2-3 only: one XOR on the address
+  unsigned abase[6][3];
+#pragma unroll
+  for (int j = 0; j < 6; ++j)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int row = (wn * 4 + j) * kFeHW + dx + col;
+      abase[j][dx] = (unsigned)(row * (kFeC * 2) + ((kg ^ (row & 15)) << 4));
+    }
+  // a weight buffer: row r (of 64), 16-byte piece c (of 8) at r * 128 + ((c ^ (r & 7)) << 4) - the swizzle of
+  // conv_igemm_kernel's 128-byte rows.  Written in load order (row 16 wv + 8 i + lane / 8, piece lane % 8), read as fragments
+  // (row 32 wm + 16 mi + col, piece 4 kk + kg).
+  const int wst = (wv * 16 + (lane >> 3)) * 128 + (((lane & 7) ^ (lane >> 3)) << 4);      // + i * 1024: the key is lane / 8
+  int wfo[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) wfo[kk] = (wm * 32 + col) * 128 + (((kk * 4 + kg) ^ (col & 7)) << 4);   // + mi * 2048: key col & 7
+  auto put_w = [&](int buf, const u32x4_ (&wr)[2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) *reinterpret_cast<u32x4_*>(wbuf[buf] + wst + i * 1024) = wr[i];
+  };
+  f32x4 acc[2][4];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+  put_w(0, wq[0]);
+#pragma unroll
+  for (int t = 0; t < kFeSteps; ++t) {
+    const int ch = t / 9, d = t - ch * 9, dy = d / 3, dx = d - dy * 3;
+    // one barrier per K step: buffer t & 1 (and, at t = 0, the hidden tile) is complete, and every wave has its fragments
+    // of step t - 1, so buffer (t + 1) & 1 may be overwritten
+    __syncthreads();
+    f16x8 af[2][2], xf[2][4];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi) af[kk][mi] = *reinterpret_cast<const f16x8*>(wbuf[t & 1] + wfo[kk] + mi * 2048);
+#pragma unroll
+      for (int ni = 0; ni < 4; ++ni)
+        xf[kk][ni] = *reinterpret_cast<const f16x8*>(hid + (abase[ni + dy][dx] ^ (unsigned)((ch * 8 + kk * 4) << 4)));
+    }
+    if (t + 1 < kFeSteps) put_w((t + 1) & 1, wq[(t + 1) % R]);
+    if (t + D < kFeSteps) load_w(t + D, wq[(t + D) % R]);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[kk][mi], xf[kk][ni], acc[mi][ni], 0, 0, 0);
+  }
+
+  // ---- epilogue (conv_epilogue_pair of conv.hip for one pair of blocks): rows 4kg .. 4kg+3 of blocks 0 and 1 are the 8
+  // consecutive channels wm*32 + 8kg .. +7 of pixel (y0 + 4 wn + ni, x0 + col); pixels past the map edge are dropped ----
+  const __amdgpu_buffer_rsrc_t rO = __builtin_amdgcn_make_buffer_rsrc((void*)out, 0, out_bytes, 0x00020000);
+  const int nch = wm * 32 + 8 * kg;
+  const float4 g0 = *reinterpret_cast<const float4*>(b3 + nch), g1 = *reinterpret_cast<const float4*>(b3 + nch + 4);
+#pragma unroll
+  for (int ni = 0; ni < 4; ++ni) {
+    const int y = y0 + wn * 4 + ni, x = x0 + col;
+    f16x8 o;
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      const f32x4 v = acc[hb][ni];
+      const float4 gg = hb ? g1 : g0;
+      o[4 * hb + 0] = (_Float16)fmaxf(v[0] + gg.x, 0.0f);
+      o[4 * hb + 1] = (_Float16)fmaxf(v[1] + gg.y, 0.0f);
+      o[4 * hb + 2] = (_Float16)fmaxf(v[2] + gg.z, 0.0f);
+      o[4 * hb + 3] = (_Float16)fmaxf(v[3] + gg.w, 0.0f);
+    }
+    const bool ok = y < H && x < W;
+    const unsigned vo = ok ? (unsigned)(((long)((n * H + y) * W + x) * os + nch) * 2) : 0x80000000u;
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, o), rO, vo, 0, 0);
+  }
+#endif
+}
+
 }  // namespace glorie
 
 using namespace glorie;
@@ -254,5 +488,29 @@ extern "C" int glorie_flow_conv7_padded(const void* padded, const void* w_packed
   hipLaunchKernelGGL(flow_conv7_padded_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const _Float16*>(padded), reinterpret_cast<const _Float16*>(w_packed), bias,
                      reinterpret_cast<_Float16*>(out), out_stride, P, H, W);
+  return check_launch();
+}
+
+extern "C" int glorie_flow_encoder(const void* padded, const void* w7_packed, const float* b7, const void* w3_packed,
+                                   const float* b3, void* out, int out_stride, int N, int H, int W, void* stream) {
+  if (N < 0 || H <= 0 || W <= 0 || out_stride < kFeNout) return GLORIE_EINVAL;
+  if (N == 0) return GLORIE_OK;
+  if (!padded || !w7_packed || !b7 || !w3_packed || !b3 || !out) return GLORIE_EINVAL;
+  // 16-byte stores of 8 channels: the caller takes the two-launch path for anything else
+  if ((out_stride & 7) || (reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(padded) & 15) ||
+      (reinterpret_cast<uintptr_t>(w3_packed) & 15) || (reinterpret_cast<uintptr_t>(w7_packed) & 15))
+    return GLORIE_EUNSUPPORTED;
+  const long P = (long)N * H * W;
+  const long fp_bytes = (long)N * (H + 2 * kFlowPadY) * (W + kFlowPadW) * 8;
+  const long out_bytes = ((P - 1) * (long)out_stride + kFeNout) * 2;
+  const long tiles_x = (W + kFeTW - 1) / kFeTW, tiles_y = (H + kFeTH - 1) / kFeTH, wgs = tiles_x * tiles_y * N;
+  // 31-bit byte offsets into the padded map and the output, a one-dimensional grid
+  if (fp_bytes >= 0x7fffffffL || out_bytes >= 0x7fffffffL || wgs >= 0x7fffffffL) return GLORIE_EUNSUPPORTED;
+  const unsigned w3_bytes = (9u * kFeNpad * kFeC + 64u) * 2u;        // pack_conv_igemm: [9][128][128] + 64 halfs
+  hipLaunchKernelGGL(flow_encoder_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const _Float16*>(padded), (unsigned)fp_bytes,
+                     reinterpret_cast<const _Float16*>(w7_packed), b7, reinterpret_cast<const _Float16*>(w3_packed),
+                     w3_bytes, b3, reinterpret_cast<_Float16*>(out), (unsigned)out_bytes, out_stride, H, W, (int)tiles_x,
+                     (int)tiles_y);
   return check_launch();
 }

@@ -301,6 +301,8 @@ class FusedUpdate:
         self._flow_pad = None     # zero-padded fp16 motion map (update_ops.PaddedFlow) for callers that pass fp32 flow
         self.fuse_glo = True      # global-context reduction inside the epilogue of its 1x1 convolution
         self.fuse_heads = True    # tap GEMMs of the delta / weight heads inside the epilogue of their hidden convolution
+        # flow encoder as one launch (glorie_flow_encoder); GLORIE_FLOW_FUSED=0 keeps its two launches
+        self.fuse_flow = os.environ.get("GLORIE_FLOW_FUSED", "1") != "0"
         self.gate_events = None   # a list: (start, end) events of every z|r gate launch are appended (eager steps only)
         self.q_events = None      # the same for the q gate launch and for the heads' hidden convolution (bench.py)
         self.heads_events = None
@@ -456,8 +458,11 @@ class FusedUpdate:
                 if self._flow_pad is None or not self._flow_pad.fits(n, ht, wd, dev):
                     self._flow_pad = U.PaddedFlow(n, ht, wd, dev)
                 pf = U.flow_pad(fl, self._flow_pad)
-            f1 = U.flow_conv7_padded(pf, W["fe1"], W["fe1_b"], cl_map(128))
-            U.conv_igemm(f1, None, W["fe2"], 9, 64, hx[:, 256:320], terms=W["fe2_b"], act=U.ACT_RELU)
+            # one launch with the hidden map in LDS (bit-identical); the two launches for an output it does not handle
+            if not (self.fuse_flow and U.flow_encoder(pf, W["fe1"], W["fe1_b"], W["fe2"], W["fe2_b"], hx[:, 256:320],
+                                                      strict=False)):
+                f1 = U.flow_conv7_padded(pf, W["fe1"], W["fe1_b"], cl_map(128))
+                U.conv_igemm(f1, None, W["fe2"], 9, 64, hx[:, 256:320], terms=W["fe2_b"], act=U.ACT_RELU)
         shared = context is not None and self.hoist_inp
         with torch.cuda.stream(side[1]):
             if shared:

@@ -432,6 +432,37 @@ def flow_conv7_padded(padded, w_packed, bias, out):
     return out
 
 
+def flow_encoder(padded, w7, b7, w3, b3, out, strict=True):
+    """the whole flow encoder (droid_net.py:79-83) as one launch (glorie_flow_encoder): out = relu(conv3x3(relu(conv7x7(
+    padded) + b7)) + b3), bit-identical to flow_conv7_padded followed by conv_igemm(.., w3, 9, 64, .., act=ACT_RELU).
+    padded: PaddedFlow; w7 / b7: pack_flow_conv7 and its float32 bias; w3 / b3: pack_conv_igemm(flow_encoder[2].weight,
+    pair=True) and its float32 bias; out: channels-last fp16 [N,64,h,w] (slice allowed).
+    Returns True.  An output the kernel does not handle (row stride not a multiple of 8 halfs, misaligned base) launches
+    nothing: GlorieError with strict, False otherwise (the caller then takes the two launches)."""
+    L.need_cuda(padded.buf, w7, b7, w3, b3, out)
+    if out.dtype != torch.float16 or out.dim() != 4 or tuple(out.shape) != (padded.n, 64, padded.h, padded.w):
+        raise RuntimeError("flow_encoder: out must be a float16 [N,64,h,w] map matching the padded motion map")
+    n, c, h, w = out.shape
+    sn, sc, sh, sw = out.stride()
+    if sc != 1 or (w > 1 and sh != w * sw) or (h * w > 1 and n > 1 and sn != h * w * sw) or sw < c:
+        raise RuntimeError("flow_encoder: out is not a channels-last map (or channel slice) with uniformly strided rows")
+    if w7.dtype != torch.float16 or tuple(w7.shape) != (128, 224) or not w7.is_contiguous():
+        raise RuntimeError("flow_encoder: w7 must come from pack_flow_conv7")
+    if w3.dtype != torch.float16 or w3.numel() != 9 * 128 * 128 + 64 or not w3.is_contiguous() \
+            or getattr(w3, "_glorie_pair", None) is not True:
+        raise RuntimeError("flow_encoder: w3 must come from pack_conv_igemm(weight [64,128,3,3], pair=True) (a copy of the "
+                           "packed tensor loses its row-layout flag: pack again)")
+    for b, k, name in ((b7, 128, "b7"), (b3, 64, "b3")):
+        if b.dtype != torch.float32 or b.numel() != k or not b.is_contiguous():
+            raise RuntimeError(f"flow_encoder: {name} must be contiguous float32 [{k}]")
+    status = L.load().glorie_flow_encoder(L.ptr(padded.buf), L.ptr(w7), L.ptr(b7), L.ptr(w3), L.ptr(b3), L.ptr(out), sw,
+                                          n, h, w, L.stream_ptr())
+    if status == -4 and not strict:            # GLORIE_EUNSUPPORTED
+        return False
+    L.check(status, "glorie_flow_encoder")
+    return True
+
+
 def flow_conv7(flow, w_packed, bias, out):
     """out = relu(conv7x7(flow) + bias); flow float32 [N,h,w,4] contiguous (channels-last motion
     map), out channels-last fp16 [N,128,h,w] (slice allowed)   (droid_net.py:79-81)"""

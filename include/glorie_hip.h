@@ -340,8 +340,18 @@ int glorie_flow_pad(const float* flow, void* padded, int N, int H, int W, void* 
 int glorie_flow_conv7_padded(const void* padded, const void* w_packed, const float* bias, void* out, int out_stride,
                              int N, int H, int W, void* stream);
 
+/* The whole flow encoder (droid_net.py:79-83) as ONE launch: out = relu(conv3x3(relu(conv7x7(padded) + b7)) + b3), the
+ * 128-channel hidden map of an 8 x 16 pixel tile (plus its one-pixel halo) kept in LDS.  padded / w7_packed / b7 as for
+ * glorie_flow_conv7_padded; w3_packed = the operand of glorie_conv_igemm for flow_encoder[2] with PAIRED rows
+ * (pack_conv_igemm(weight [64,128,3,3], pair=True): [9][128][128] halfs + 64), b3 float32 [64]; out: fp16 rows of 64
+ * channels, out_stride halfs apart.  Bit-identical to glorie_flow_conv7_padded followed by glorie_conv_igemm (3x3, 64
+ * outputs, bias + ReLU) on the same operands.  GLORIE_EUNSUPPORTED (nothing launched) when out_stride % 8 != 0, a pointer
+ * is not 16-byte aligned or a byte offset exceeds 31 bits: the caller takes the two launches. */
+int glorie_flow_encoder(const void* padded, const void* w7_packed, const float* b7, const void* w3_packed, const float* b3,
+                        void* out, int out_stride, int N, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------------------------ */
-/* A/B. projective geometry                                                              */
+/* A/B. projective geometry                                                             */
 /* ------------------------------------------------------------------------------------ */
 
 /* pops.projective_transform(jacobian=False) via DepthVideo.reproject
