@@ -747,6 +747,11 @@ class SequenceRunner:
         return {"keyframes": int(self.video.counter.value), "final_ba_edges": int(n_edges), "mapped": self.mapped,
                 "points": int(self.npc.pts_num()), "losses": list(self.losses), "timing": self.timing}
 
+    def run_stream(self, stream, **kwargs):
+        """run() over a dataset stream (datasets.BaseDataset: items (index, color [1,3,H,W], depth, pose) and
+        get_intrinsic()): the frame index is the timestamp, as in the reference's tracker loop (src/tracker.py:48-51)"""
+        return self.run(((item[0], item[1]) for item in stream), stream.get_intrinsic(), **kwargs)
+
     # ---- eval_render.py:18-124 ------------------------------------------------------------------------------------------
     def evaluate(self, output=None, gt_depth_fn=None, **kwargs):
         """re-render every mapped keyframe and score it against its image (eval_render.eval_kf_imgs: PSNR, MS-SSIM, their

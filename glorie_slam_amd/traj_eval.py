@@ -6,6 +6,9 @@ absolute position error.  numpy float64 on the host - a few hundred poses.
   align_kf_traj    the alignment of the keyframes of video.npz to ground-truth poses by timestamp
   ape_statistics   rmse, mean, median, std, min, max, sse of the translation part
   kf_traj_eval     writes metrics_kf_traj.txt and stores `scale` back into video.npz
+  align_full_traj  the alignment of every frame's pose to a stream's ground truth (eval_traj.py:42-65)
+  full_traj_eval   the trajectory filler over a dataset stream, keyframes from the video; writes metrics_full_traj.txt
+                   (eval_traj.py:137-169)
 
 A monocular map has no metric scale: generate_mesh.generate_mesh_kf takes the scale and the 4x4 of this alignment.
 Out of scope: the trajectory plots and the camera visualiser (matplotlib).
@@ -97,3 +100,51 @@ def kf_traj_eval(video_npz, out_dir, gt):
     video["scale"] = np.array(s)
     np.savez(video_npz, **video)
     return stats, s, r_a, t_a
+
+
+def align_full_traj(traj_est_full, gt_poses):
+    """src/utils/eval_traj.py:42-65.  traj_est_full [n,4,4] c2w of every frame, gt_poses: n ground-truth c2w (a stream's
+    `poses`).  The frames whose ground-truth pose holds NaN or Inf are skipped.
+    -> (r_a, t_a, s, est_poses, ref_poses): the aligned estimates and the ground truth of the kept frames"""
+    full = np.asarray(traj_est_full, np.float64)
+    if len(gt_poses) != len(full):
+        raise ValueError(f"{len(full)} estimated poses, {len(gt_poses)} ground-truth poses")
+    est, ref = [], []
+    for i in range(len(gt_poses)):
+        gt = np.asarray(gt_poses[i], np.float64)
+        if not np.isfinite(gt.sum()):
+            continue
+        est.append(full[i])
+        ref.append(gt)
+    if len(est) < 3:
+        raise ValueError("fewer than 3 frames have a finite ground-truth pose")
+    est, ref = np.stack(est), np.stack(ref)
+    r_a, t_a, s = umeyama(est[:, :3, 3], ref[:, :3, 3], with_scale=True)
+    return r_a, t_a, s, _apply(est, r_a, t_a, s), ref
+
+
+def full_traj_eval(traj_filler, out_dir, stream):
+    """src/utils/eval_traj.py:137-169: the pose of every frame of `stream` from the trajectory filler (a
+    PoseTrajectoryFiller; world-to-camera, inverted here), the keyframes' entries overwritten with the keyframes' own
+    poses, aligned to stream.poses; writes out_dir/metrics_full_traj.txt.
+    -> (traj_est_not_aligned [n,4,4], traj_est_aligned [m,4,4], traj_ref [m,4,4]) float64 numpy, m = the frames with a
+    finite ground-truth pose"""
+    from . import lie
+    video = traj_filler.video
+    traj_est = traj_filler(stream).inv().matrix().detach().cpu().numpy().astype(np.float64)
+    kf_num = video.counter.value
+    kf_timestamps = video.timestamp[:kf_num].cpu().int().numpy()
+    kf_poses = lie.SE3(video.poses[:kf_num].clone()).inv().matrix().detach().cpu().numpy()
+    traj_est[kf_timestamps] = kf_poses
+    traj_est_not_aligned = traj_est.copy()
+    r_a, t_a, s, est, ref = align_full_traj(traj_est, stream.poses)
+    stats = ape_statistics(est, ref)
+    os.makedirs(out_dir, exist_ok=True)
+    text = "#" * 10 + "Full traj" + "#" * 10 + "\n"
+    text += f"scale: {s}\n"
+    text += f"rotation:\n{r_a}\n"
+    text += f"translation:{t_a}\n"
+    text += f"statistics:\n{stats}"
+    with open(os.path.join(out_dir, "metrics_full_traj.txt"), "w+") as fp:
+        fp.write(text)
+    return traj_est_not_aligned, est, ref

@@ -1074,6 +1074,37 @@ int glorie_window_rays(const void* depth_table, const void* image_table, const v
                        const int64_t* jj, float const_radius, int want_radius, float* rays_o, float* rays_d, float* depth,
                        float* color, float* radius, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Frame ingest (dataset streams)                                                        */
+/* ------------------------------------------------------------------------------------ */
+
+/* A batch of raw colour frames -> working-size float images
+ *   reference: src/utils/datasets.py:60-83 (get_color), :98-113 (__getitem__): cv2.undistort, cv2.resize, crop, / 255
+ * frames uint8 [B,H,W,3] -> out f32 [B,3,H_out,W_out] in [0,1].  Integer arithmetic up to the last step; the tables depend
+ * on the camera only and are built once on the host (glorie_slam_amd/ingest.py):
+ *   map   NULL (no undistortion) or int32 [H,W,2] = (ix, iy), the source position of the undistorted pixel in 1/32 pixel.
+ *         mid(u,v) = (sum_w p + 512) >> 10 over the taps (ix>>5 + i, iy>>5 + j), i, j in {0,1}, with weights
+ *         (32-a)(32-b), a(32-b), (32-a)b, ab, a = ix & 31, b = iy & 31; a tap outside the image contributes 0.  Without a
+ *         map mid = the frame.
+ *   xtab  int32 [W_out,4] = (s0, s1, a0, a1) per output column: row(y) = mid(s0,y) a0 + mid(s1,y) a1, a0 + a1 = 2048
+ *   ytab  int32 [H_out,4] = (s0, s1, b0, b1) per output row:
+ *         level = (((b0 (row(s0) >> 4)) >> 16) + ((b1 (row(s1) >> 4)) >> 16) + 2) >> 2
+ *         (the crop is the choice of the table rows; indices are clamped to the frame before use)
+ *   lut   f32 [256]: lut[level] = float32(level) / float32(255), correctly rounded
+ * swap_rb: output channel c is input channel 2 - c.  mid is rounded to a level before the resize, as two whole-image
+ * passes would, and never stored.  B = 0 launches nothing.  One launch, no workspace, no host synchronisation. */
+int glorie_ingest_color(const uint8_t* frames, int B, int H, int W, const int32_t* map, const int32_t* xtab,
+                        const int32_t* ytab, const float* lut, int H_out, int W_out, int swap_rb, float* out, void* stream);
+/* A batch of raw depth maps -> working-size float depth   reference: src/utils/datasets.py:48-58, :115-130
+ * raw [B,H,W] uint16 (dtype GLORIE_INGEST_U16) or f32 (GLORIE_INGEST_F32) -> out f32 [B,H_out,W_out]:
+ * out[b,y,x] = float32(raw[b, ysrc[y], xsrc[x]]) / scale, correctly rounded; ysrc int32 [H_out], xsrc int32 [W_out] hold
+ * the nearest-neighbour source indices (already cropped; clamped to the map before use).  Depth is never undistorted.
+ * One launch, no host synchronisation. */
+#define GLORIE_INGEST_U16 0
+#define GLORIE_INGEST_F32 1
+int glorie_ingest_depth(const void* raw, int dtype, int B, int H, int W, const int32_t* ysrc, const int32_t* xsrc,
+                        float scale, int H_out, int W_out, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
