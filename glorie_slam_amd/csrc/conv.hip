@@ -19,8 +19,7 @@
 //   fragment reads -> barrier (every wave holds its fragments: the stage is free) -> DMA of the
 //   next tile into the same stage -> 32 MFMAs from registers while it streams in.  Occupancy plus
 //   this register-level double buffering measured faster than two or three LDS stages with fewer
-//   resident workgroups (ST = 2 is kept as a template variant; the other measurements are listed at
-//   the dispatch below).  The LDS image is
+//   resident workgroups (the measurements are listed at the dispatch below).  The LDS image is
 //   lane-linear as the DMA requires; the 16-byte slot of a row is XOR-swizzled on the SOURCE
 //   address and on the fragment read (conflict-free b128 reads).
 // * Zero padding: a lane whose row is outside the map for the current tap sets bit 31 of its
@@ -80,62 +79,11 @@ __device__ __forceinline__ float ctanh(float x) {
   return copysignf((1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), x);
 }
 
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
 // pixel of `pre` that output pixel p reads: maps that share their context features share one map of the term
 __device__ __forceinline__ long pre_pixel(const ConvArgs& a, long p) {
   if (!a.pre_map) return p;
   const int e = (int)(p / a.HW);
   return (long)a.pre_map[e] * a.HW + (p - (long)e * a.HW);
-}
-
-// fused epilogue for the 4 consecutive output channels n..n+3 of pixel p (map e): bias + activation, the GRU gates
-// (z = sigmoid, r * net) or the GRU blend
-template <int EPI>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const f32x4 v, long p, int e, int n) {
-  f16x4 o;
-  if (EPI == EPI_BIAS_ACT) {
-    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a.terms) b = *reinterpret_cast<const float4*>(a.terms + n);
-    float f[4] = {v[0] + b.x, v[1] + b.y, v[2] + b.z, v[3] + b.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (a.act == CACT_RELU) f[k] = fmaxf(f[k], 0.0f);
-      else if (a.act == CACT_SIGMOID) f[k] = csigmoid(f[k]);
-      o[k] = (_Float16)f[k];
-    }
-    *reinterpret_cast<f16x4*>(a.out + p * a.out_stride + n) = o;
-  } else if (EPI == EPI_GRU_ZR) {
-    // channels 0..127: z = sigmoid(.) ; 128..255: r -> r * net          (gru.py:28-30)
-    const float4 g = *reinterpret_cast<const float4*>(a.terms + (size_t)e * a.terms_stride + n);
-    const float s[4] = {csigmoid(v[0] + g.x), csigmoid(v[1] + g.y), csigmoid(v[2] + g.z),
-                        csigmoid(v[3] + g.w)};
-    if (n < 128) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = (_Float16)s[k];
-      *reinterpret_cast<f16x4*>(a.out + p * a.out_stride + n) = o;
-    } else {
-      const f16x4 nv = *reinterpret_cast<const f16x4*>(a.net + p * a.net_stride + (n - 128));
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = (_Float16)(s[k] * (float)nv[k]);
-      *reinterpret_cast<f16x4*>(a.out2 + p * a.out2_stride + (n - 128)) = o;
-    }
-  } else {
-    // net' = (1 - z) * net + z * tanh(.)                                (gru.py:31-33)
-    const float4 g = *reinterpret_cast<const float4*>(a.terms + (size_t)e * a.terms_stride + n);
-    const f16x4 nv = *reinterpret_cast<const f16x4*>(a.net + p * a.net_stride + n);
-    const f16x4 zv = *reinterpret_cast<const f16x4*>(a.z + p * a.z_stride + n);
-    const float qv[4] = {ctanh(v[0] + g.x), ctanh(v[1] + g.y), ctanh(v[2] + g.z), ctanh(v[3] + g.w)};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float zz = (float)zv[k];
-      o[k] = (_Float16)((1.0f - zz) * (float)nv[k] + zz * qv[k]);
-    }
-    *reinterpret_cast<f16x4*>(a.out + p * a.out_stride + n) = o;
-  }
 }
 
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
@@ -534,110 +482,212 @@ __device__ __forceinline__ void conv_epilogue_upsample(const ConvArgs& a, f32x4 
   *reinterpret_cast<float4*>(dst) = make_float4(outv[0], outv[1], outv[2], outv[3]);
 }
 
-// NB = 16-pixel blocks per wave, BK = channels per K step (32 | 64), NW = waves (2 channel halves x
-// NW/2 pixel groups: pixel tile = NW/2 * 16*NB), ST = LDS stages (1: single stage + register-resident
-// fragments, the shipped form; 2: classic double buffering with one __syncthreads per step)
-template <int EPI, int NB, int BK, int NW, int ST, int MB = 4>
-__global__ __launch_bounds__(64 * NW, (ST == 1 && MB * NB <= 16) ? 3 : 2) void conv_igemm_kernel(ConvArgs a) {
-  constexpr int TN = 32 * MB;               // output channels per workgroup (MB 16-channel blocks per wave)
-  static_assert(ST == 1 || ST == 2, "LDS stages");
+// ------------------------------------------------------------------------------------------------------------------
+// Pieces shared by the four kernel families below (conv_igemm_kernel, conv_halo_kernel, conv_pp_kernel, conv_ppw_kernel).
+// All of them stage K-tiles of 64 channels: a staged row is 128 bytes = 8 slots of 16 bytes, one wave-wide DMA instruction
+// fills 8 rows and a K-tile is two 32-channel MFMA steps.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int RB = 128;                     // bytes per staged row
+constexpr int SL = RB / 16;                 // 16-byte slots per row
+constexpr int RPI = 64 / SL;                // rows per wave-wide DMA instruction
+constexpr int KK = 2;                       // MFMA steps per K-tile
+
+// XCD-aware (bijective) remap of workgroup j of a range of nwg workgroups: consecutive results run on one XCD
+template <typename I>                                 // (unsigned for blockIdx.x itself, int for an offset into a range)
+__device__ __forceinline__ int xcd_remap(I j, int nwg) {
+  const int xcd = j & 7, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (j >> 3);
+}
+// remapped workgroup id -> (pixel tile, output-channel tile) of a launch with ntn channel tiles per pixel tile
+struct TileId { int lid, pt, nt; bool full; };
+__device__ __forceinline__ TileId tile_id_of(int lid, int ntn, bool full) {
+  TileId t;
+  t.lid = lid; t.pt = lid / ntn; t.nt = lid - t.pt * ntn; t.full = full;
+  return t;
+}
+__device__ __forceinline__ TileId tile_id(int ntn) { return tile_id_of(xcd_remap(blockIdx.x, gridDim.x), ntn, true); }
+// the two-range form of the ping-pong kernels: workgroups [0, nfull) hold full tiles, the others the smaller tiles of the
+// partial round (pt counts from 0 again); each range is spread over the XCDs on its own (nfull is a multiple of 8)
+__device__ __forceinline__ TileId tile_id(int ntn, int nfull) {
+  const int bid = blockIdx.x;
+  const bool full = bid < nfull;
+  const int base = full ? 0 : nfull, nwg = full ? nfull : (int)gridDim.x - nfull;
+  return tile_id_of(xcd_remap(bid - base, nwg), ntn, full);
+}
+
+// tap validity of pixel p: bit d = tap d reads a pixel of the same map (3x3), bit 0 alone for 1x1; 0 past the end
+// (only3x3: the caller runs 3x3 layers only)
+__device__ __forceinline__ unsigned tap_mask(const ConvArgs& a, long p, bool only3x3 = false) {
+  unsigned m = 0;
+  if (p < a.P) {
+    const int pi_ = (int)p, xw = pi_ % a.W, yh = (pi_ / a.W) % a.H;      // p < P < 2^31 (the 31-bit offset check of the launch)
+    if (only3x3 || a.taps == 9) {
+#pragma unroll
+      for (int d = 0; d < 9; ++d) {
+        const int dy = d / 3 - 1, dx = d % 3 - 1;
+        if ((unsigned)(yh + dy) < (unsigned)a.H && (unsigned)(xw + dx) < (unsigned)a.W) m |= 1u << d;
+      }
+    } else {
+      m = 1;
+    }
+  }
+  return m;
+}
+
+// Staging through buffer descriptors: address = base + SGPR offset (tap shift, channel chunk:
+// wave-uniform, changes per step) + VGPR offset (row, swizzled slot: per lane, loop-invariant).
+// A lane whose row falls outside the map for this tap gets bit 31 set in its VGPR offset: the
+// hardware range check fails and the DMA writes ZEROS into LDS -- zero padding costs three VALU
+// instructions per load and no branch.  The descriptor of an input segment sits `back` rows before
+// the tensor so that the SGPR offset of the (-1,-1) tap is not negative.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_rsrc(const _Float16* base, int back = 0, int stride = 0) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(base - (long)back * stride), 0, 0x7fffffff, 0x00020000);
+}
+__device__ __forceinline__ int tap_back(const ConvArgs& a) { return a.taps == 9 ? a.W + 1 : 0; }
+// staging role of a lane in staging slot w (of NW): DMA instruction i fills rows (i * NW + w) * RPI .. + RPI - 1, the lane
+// its row `srow` of them.  Rows of consecutive instructions are NW * RPI apart and share the swizzle key (row & 7: ds_read_b128
+// of 16 consecutive rows is conflict-free for the hardware's lane groups, brute-force checked), so one VGPR offset per operand
+// serves all of them: instruction i adds i * NW * RPI rows to the SGPR offset
+struct StageLane { int srow, slot, row0, sw0; };
+__device__ __forceinline__ StageLane stage_lane(int lane, int w) {
+  StageLane s;
+  s.srow = lane / SL; s.slot = lane % SL;
+  s.row0 = w * RPI + s.srow;
+  s.sw0 = (s.slot ^ (s.row0 & 7)) << 3;              // swizzled 16-byte slot, in halfs
+  return s;
+}
+__device__ __forceinline__ unsigned stage_voff(const StageLane& s, long first_row, int stride) {     // pixel rows
+  return (unsigned)(((first_row + s.row0) * stride + s.sw0) * 2);
+}
+__device__ __forceinline__ unsigned stage_woff(const StageLane& s, int C) {                          // weight rows of C channels
+  return (unsigned)(((size_t)s.row0 * C + s.sw0) * 2);
+}
+
+template <int MB, int NB>
+__device__ __forceinline__ void clear_acc(f32x4 (&acc)[MB][NB]) {
+#pragma unroll
+  for (int mi = 0; mi < MB; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NB; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+// fragment reads: row = 16 * blk + col, logical slot kk * 4 + kg, swizzle key = row & 7 = col & 7
+__device__ __forceinline__ void frag_offsets(int (&foff)[KK], int col, int kg) {
+#pragma unroll
+  for (int kk = 0; kk < KK; ++kk) foff[kk] = col * RB + (((kk * 4 + kg) ^ (col & 7)) << 4);
+}
+template <int MB, int NB>
+__device__ __forceinline__ void read_frags(f16x8 (&wf)[KK][MB], f16x8 (&xf)[KK][NB], const char* bw, const char* bx,
+                                           const int (&foff)[KK]) {
+#pragma unroll
+  for (int kk = 0; kk < KK; ++kk) {
+#pragma unroll
+    for (int mi = 0; mi < MB; ++mi) wf[kk][mi] = *reinterpret_cast<const f16x8*>(bw + mi * 16 * RB + foff[kk]);
+#pragma unroll
+    for (int ni = 0; ni < NB; ++ni) xf[kk][ni] = *reinterpret_cast<const f16x8*>(bx + ni * 16 * RB + foff[kk]);
+  }
+}
+template <int MB, int NB>
+__device__ __forceinline__ void mfma_tile(f32x4 (&acc)[MB][NB], const f16x8 (&wf)[KK][MB], const f16x8 (&xf)[KK][NB]) {
+#pragma unroll
+  for (int kk = 0; kk < KK; ++kk)
+#pragma unroll
+    for (int mi = 0; mi < MB; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NB; ++ni)
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kk][mi], xf[kk][ni], acc[mi][ni], 0, 0, 0);
+}
+
+// epilogue of the 4-wave kernels (2 channel halves wm x 2 pixel halves wn): the lane owns channels n0 + wm*16*MB + mi*16 +
+// kg*4 .. +3 of pixel p0 + wn*16*NB + ni*16 + col.  The epilogues that reduce through LDS exist for the 128 x 128 tile only
+template <int EPI, int MB, int NB>
+__device__ __forceinline__ void conv_finish_tile(const ConvArgs& a, f32x4 (&acc)[MB][NB], long p0, int n0, const TileId& id,
+                                                 char* smem) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int col = lane & 15, kg = lane >> 4;
+  const int wm = wv & 1, wn = wv >> 1;
+  constexpr bool k128 = MB == 4 && NB == 4;
+  if constexpr (EPI == EPI_GLO) {
+    if constexpr (k128) conv_epilogue_glo<MB, NB>(a, acc, p0, p0 + wn * (16 * NB) + col, wm, wn, kg, col, smem, id.pt);
+  } else if constexpr (EPI == EPI_UPSAMPLE) {
+    if constexpr (k128) conv_epilogue_upsample<MB, NB>(a, acc, p0, n0, wm, wn, kg, col, smem);
+  } else if constexpr (EPI == EPI_HEADS) {
+    if constexpr (k128) {
+      if (id.nt < a.tap_groups)                                                 // workgroup-uniform
+        conv_epilogue_heads<MB, NB>(a, acc, p0, n0, wm, wn, kg, col, lane, smem);
+      else
+        conv_epilogue_tile<EPI_BIAS_ACT, MB, NB>(a, acc, p0 + wn * (16 * NB) + col, n0 + wm * (16 * MB) + kg * 4,
+                                                 a.tap_groups * 128);
+    }
+  } else {
+    conv_epilogue_tile<EPI, MB, NB>(a, acc, p0 + wn * (16 * NB) + col, n0 + wm * (16 * MB) + kg * 4);
+  }
+}
+
+// EXP_CONV_STAMPS builds (tools/conv_timeline.sh, tools/conv_pp_timeline.sh): shader-clock stamps of K-tiles 10-13 of every
+// `every`-th workgroup (16 of them) into ConvArgs.stamps as [16][nw waves][4 K-tiles][nk checkpoints].  Expects a, lane, wv
+// and t in scope; workgroups with lid < 0 are not stamped
+#ifdef EXP_CONV_STAMPS
+#define CONV_STAMP(lid, every, nw, nk, k) do {                                                                        \
+    if (a.stamps && lane == 0 && (lid) >= 0 && (lid) % (every) == 0 && (lid) / (every) < 16 && t >= 10 && t < 14) {   \
+      unsigned long long ts_;                                                                                         \
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts_) : : "memory");                                  \
+      a.stamps[(((lid) / (every) * (nw) + wv) * 4 + (t - 10)) * (nk) + (k)] = ts_; } } while (0)
+#else
+#define CONV_STAMP(lid, every, nw, nk, k)
+#endif
+
+// NB = 16-pixel blocks per wave, MB = 16-channel blocks per wave; 4 waves (2 channel halves x 2 pixel halves): the workgroup
+// tile is 32 MB channels x 32 NB pixels in one LDS stage, the fragments of a step register-resident
+template <int EPI, int NB, int MB = 4>
+__global__ __launch_bounds__(256, MB * NB <= 16 ? 3 : 2) void conv_igemm_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (buffer-resource types are device-only)
-  constexpr int PT = (NW / 2) * 16 * NB;      // pixels per workgroup
-  constexpr int RB = BK * 2;                  // bytes per staged row
-  constexpr int SL = RB / 16;                 // 16-byte slots per row
-  constexpr int RPI = 64 / SL;                // rows per wave-wide DMA instruction
+  constexpr int NW = 4;                       // waves
+  constexpr int TN = 32 * MB;                 // output channels per workgroup
+  constexpr int PT = 32 * NB;                 // pixels per workgroup
   constexpr int XI = PT / RPI / NW;           // DMA instructions per wave per step: pixel tile
   constexpr int WI = TN / RPI / NW;           //                                      weight tile
-  constexpr int XBYTES = PT * RB, WBYTES = TN * RB;
-  constexpr int KK = BK / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // ST x (pixel tile, weight tile), one array
+  constexpr int XBYTES = PT * RB;
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // (pixel tile, weight tile), one array
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int col = lane & 15, kg = lane >> 4;
   const int wm = wv & 1, wn = wv >> 1;
 
-  // 16-byte slot swizzle key of an LDS row: ds_read_b128 of 16 consecutive rows is conflict-free for
-  // the hardware's lane groups ({0-3,12-15,20-27}, ...) with these keys (brute-force checked)
-  auto key = [](int row) { return RB == 128 ? (row & 7) : ((row >> 1) & 3); };
-
-  // XCD-aware (bijective) remap of the workgroup id, then (pixel tile, output-channel tile)
-  const int nwg = gridDim.x, ntn = (a.nout + TN - 1) / TN;
-  const int xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-  const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-  const int pt = lid / ntn, nt = lid - pt * ntn;
+  const TileId id = tile_id((a.nout + TN - 1) / TN);
   // EPI_GLO tiles every map separately (ceil(HW / PT) tiles per map, the last one ragged): the grouping of a map's pixel
   // sums then does not depend on where the map sits in the batch (the result is invariant under edge permutations)
   const int tpm = (a.HW + PT - 1) / PT;
-  const long p0 = EPI == EPI_GLO ? (long)(pt / tpm) * a.HW + (long)(pt % tpm) * PT : a.pbeg + (long)pt * PT;
-  const int n0 = nt * TN;
+  const long p0 = EPI == EPI_GLO ? (long)(id.pt / tpm) * a.HW + (long)(id.pt % tpm) * PT : a.pbeg + (long)id.pt * PT;
+  const int n0 = id.nt * TN;
 
-  const int cpc = 64 / BK;                    // K steps per 64-channel chunk
-  const int nsteps_tap = (a.cha + a.chb) * cpc;
   const int C = (a.cha + a.chb) * 64;
-  const int T = a.taps * nsteps_tap;
+  const int T = a.taps * (a.cha + a.chb);
 
-  // Staging through buffer descriptors: address = base + SGPR offset (tap shift, channel chunk:
-  // wave-uniform, changes per step) + VGPR offset (row, swizzled slot: per lane, loop-invariant).
-  // A lane whose row falls outside the map for this tap gets bit 31 set in its VGPR offset: the
-  // hardware range check fails and the DMA writes ZEROS into LDS -- zero padding costs three VALU
-  // instructions per load and no branch.  The descriptor base sits `back` rows before the tensor
-  // so that the SGPR offset of the (-1,-1) tap is not negative.
-  const int back = a.taps == 9 ? a.W + 1 : 0;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.xa - (long)back * a.xa_stride), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.xb - (long)back * a.xb_stride), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x7fffffff, 0x00020000);
-
-  // staging roles: DMA instruction i of wave wv fills rows (i*4 + wv)*RPI .. +RPI-1; lane -> (row, slot)
-  const int srow = lane / SL, slot = lane % SL;
-  // rows of consecutive instructions are NW * RPI apart and share the swizzle key (it depends on the row modulo RPI
-  // only), so one VGPR offset per operand serves all of them: instruction i adds i * NW * RPI rows to the SGPR offset
-  const int row0 = wv * RPI + srow;
-  const int sw0 = (slot ^ key(row0)) << 3;           // swizzled 16-byte slot, in halfs
-  const unsigned voffA0 = (unsigned)(((p0 + row0) * a.xa_stride + sw0) * 2);
-  const unsigned voffB0 = (unsigned)(((p0 + row0) * a.xb_stride + sw0) * 2);
-  const unsigned woff0 = (unsigned)(((size_t)row0 * C + sw0) * 2);
-  int vmask[XI];                                     // rows past the end have no valid tap: their loads are dropped
+  const int back = tap_back(a);
+  const __amdgpu_buffer_rsrc_t rA = conv_rsrc(a.xa, back, a.xa_stride), rB = conv_rsrc(a.xb, back, a.xb_stride);
+  const __amdgpu_buffer_rsrc_t rW = conv_rsrc(a.w);
+  const StageLane sl = stage_lane(lane, wv);
+  const unsigned voffA0 = stage_voff(sl, p0, a.xa_stride), voffB0 = stage_voff(sl, p0, a.xb_stride);
+  const unsigned woff0 = stage_woff(sl, C);
+  unsigned vmask[XI];                                // rows past the end have no valid tap: their loads are dropped
 #pragma unroll
-  for (int i = 0; i < XI; ++i) {
-    const long p = p0 + (i * NW + wv) * RPI + srow;
-    int m = 0;
-    if (p < a.P) {
-      const int pi_ = (int)p, xw = pi_ % a.W, yh = (pi_ / a.W) % a.H;      // p < P < 2^31 (the 31-bit offset check of the launch)
-      if (a.taps == 9) {
-#pragma unroll
-        for (int d = 0; d < 9; ++d) {
-          const int dy = d / 3 - 1, dx = d % 3 - 1;
-          if ((unsigned)(yh + dy) < (unsigned)a.H && (unsigned)(xw + dx) < (unsigned)a.W) m |= 1 << d;
-        }
-      } else {
-        m = 1;
-      }
-    }
-    vmask[i] = m;
-  }
+  for (int i = 0; i < XI; ++i) vmask[i] = tap_mask(a, p0 + (i * NW + wv) * RPI + sl.srow);
 
-  auto stage = [&](int t, int buf) {
+  auto stage = [&](int t) {
     // K order: 64-channel chunk outermost, the taps inside it -- the 9 shifted reads of a chunk of
     // the workgroup's pixel rows follow each other, so all but the first hit L2 (tap-major order
     // has a reuse distance of the whole [pixels x C] panel of every resident workgroup: > L2)
-    const int per_chunk = a.taps * cpc;
-    const int ch = t / per_chunk, rem = t - ch * per_chunk;
-    const int d = rem / cpc, sub = rem - d * cpc;        // tap, BK-wide part of the 64-channel chunk
+    const int ch = t / a.taps, d = t - ch * a.taps;
     const int shift = (a.taps == 9 ? (d / 3 - 1) * a.W + (d % 3 - 1) : 0) + back;
     const bool segA = ch < a.cha;
     const int xs = segA ? a.xa_stride : a.xb_stride;
-    const unsigned xsoff = (unsigned)((shift * xs + (segA ? ch : ch - a.cha) * 64 + sub * BK) * 2);
-    const unsigned wsoff = (unsigned)((((size_t)d * a.npad + n0) * C + ch * 64 + sub * BK) * 2);
-    char* lx = smem + buf * (XBYTES + WBYTES);
+    const unsigned xsoff = (unsigned)((shift * xs + (segA ? ch : ch - a.cha) * 64) * 2);
+    const unsigned wsoff = (unsigned)((((size_t)d * a.npad + n0) * C + ch * 64) * 2);
+    char* lx = smem;
     char* lw = lx + XBYTES;
     const unsigned xstep = (unsigned)(NW * RPI * xs * 2), wstep = (unsigned)(NW * RPI * C * 2);
-#ifdef EXP_NO_PIXEL_DMA
-    if (d == 0)                                  // ablation: the pixel tile is staged once per chunk (wrong results)
-#endif
 #pragma unroll
     for (int i = 0; i < XI; ++i) {
-      const unsigned inv = ~((unsigned)vmask[i] >> d);
+      const unsigned inv = ~(vmask[i] >> d);
       const unsigned vo = (inv << 31) | (segA ? voffA0 : voffB0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(segA ? rA : rB,
           (__attribute__((address_space(3))) void*)(lx + (i * NW + wv) * RPI * RB), 16, vo, xsoff + i * xstep, 0, 0);
@@ -649,28 +699,13 @@ __global__ __launch_bounds__(64 * NW, (ST == 1 && MB * NB <= 16) ? 3 : 2) void c
   };
 
   f32x4 acc[MB][NB];
-#pragma unroll
-  for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NB; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // fragment reads: row = 16*blk + col, logical slot kk*4 + kg, swizzle key(row) = key(col)
+  clear_acc(acc);
   int foff[KK];
-#pragma unroll
-  for (int kk = 0; kk < KK; ++kk) foff[kk] = col * RB + (((kk * 4 + kg) ^ key(col)) << 4);
+  frag_offsets(foff, col, kg);
   const int wbase = XBYTES + wm * (16 * MB) * RB, xbase_l = wn * (16 * NB) * RB;
 
-#ifdef EXP_CONV_STAMPS
-  // experiment (tools/conv_timeline.sh): shader-clock stamps of K-tiles 10-13 of every 61st workgroup, [16][NW][4][8]
-  const int swg = lid / 61;
-#define CV_STAMP(k) do { if (a.stamps && lane == 0 && lid % 61 == 0 && swg < 16 && t >= 10 && t < 14) { unsigned long long ts_;   \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts_) : : "memory");                                              \
-    a.stamps[((swg * NW + wv) * 4 + (t - 10)) * 8 + (k)] = ts_; } } while (0)
-#else
-#define CV_STAMP(k)
-#endif
-  stage(0, 0);
-  int cur = 0;                                 // LDS stage holding tile t
+#define CV_STAMP(k) CONV_STAMP(id.lid, 61, NW, 8, k)
+  stage(0);
   for (int t = 0; t < T; ++t) {
     CV_STAMP(0);
     // every DMA piece of tile t must have landed before anybody reads it.  The compiler's own wait in front of the barrier
@@ -679,62 +714,26 @@ __global__ __launch_bounds__(64 * NW, (ST == 1 && MB * NB <= 16) ? 3 : 2) void c
     // of the shipped variants spills, but the wait is explicit now.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     CV_STAMP(1);
-    __syncthreads();                           // tile t landed (vmcnt(0) + barrier); ST = 2: the other stage is free
+    __syncthreads();                           // tile t landed (vmcnt(0) + barrier)
     CV_STAMP(2);
-    const char* base = smem + cur * (XBYTES + WBYTES);
     // all fragment reads of the step go out first (one exposed LDS latency per step, not per kk), the
     // DMA of the next tile is issued in their shadow, then the MFMAs run back to back
     f16x8 wf[KK][MB], xf[KK][NB];
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-#pragma unroll
-      for (int mi = 0; mi < MB; ++mi)
-        wf[kk][mi] = *reinterpret_cast<const f16x8*>(base + wbase + mi * 16 * RB + foff[kk]);
-#pragma unroll
-      for (int ni = 0; ni < NB; ++ni)
-        xf[kk][ni] = *reinterpret_cast<const f16x8*>(base + xbase_l + ni * 16 * RB + foff[kk]);
-    }
-    if (ST == 1) {
-      // single LDS stage, 3 workgroups per CU.  Every fragment of the step is in registers now, so
-      // once all waves got theirs the buffer is free: tile t+1 streams into it under the MFMAs.
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      CV_STAMP(3);
-      __builtin_amdgcn_s_barrier();
-      CV_STAMP(4);
-      if (t + 1 < T) stage(t + 1, 0);
-      CV_STAMP(5);
-    } else {
-      if (t + 1 < T) stage(t + 1, cur ^ 1);
-    }
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-      for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NB; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kk][mi], xf[kk][ni], acc[mi][ni], 0, 0, 0);
+    read_frags(wf, xf, smem + wbase, smem + xbase_l, foff);
+    // single LDS stage, 3 workgroups per CU.  Every fragment of the step is in registers now, so
+    // once all waves got theirs the buffer is free: tile t+1 streams into it under the MFMAs.
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    CV_STAMP(3);
+    __builtin_amdgcn_s_barrier();
+    CV_STAMP(4);
+    if (t + 1 < T) stage(t + 1);
+    CV_STAMP(5);
+    mfma_tile(acc, wf, xf);
     CV_STAMP(6);
-    if (ST == 2) cur ^= 1;
   }
+#undef CV_STAMP
 
-  // ---- epilogue: lane owns channels n0 + wm*16*MB + mi*16 + kg*4 .. +3 of pixel p0 + wn*16*NB + ni*16 + col ----
-  if constexpr (EPI == EPI_GLO) {
-    if constexpr (MB == 4 && NB == 4 && NW == 4 && ST == 1)
-      conv_epilogue_glo<MB, NB>(a, acc, p0, p0 + wn * (16 * NB) + col, wm, wn, kg, col, smem, pt);
-  } else if constexpr (EPI == EPI_UPSAMPLE) {
-    if constexpr (MB == 4 && NB == 4 && NW == 4 && ST == 1)
-      conv_epilogue_upsample<MB, NB>(a, acc, p0, n0, wm, wn, kg, col, smem);
-  } else if constexpr (EPI == EPI_HEADS) {
-    if constexpr (MB == 4 && NB == 4 && NW == 4 && ST == 1) {
-      if (nt < a.tap_groups)                                                    // workgroup-uniform
-        conv_epilogue_heads<MB, NB>(a, acc, p0, n0, wm, wn, kg, col, lane, smem);
-      else
-        conv_epilogue_tile<EPI_BIAS_ACT, MB, NB>(a, acc, p0 + wn * (16 * NB) + col, n0 + wm * (16 * MB) + kg * 4,
-                                                 a.tap_groups * 128);
-    }
-  } else {
-    conv_epilogue_tile<EPI, MB, NB>(a, acc, p0 + wn * (16 * NB) + col, n0 + wm * (16 * MB) + kg * 4);
-  }
+  conv_finish_tile<EPI>(a, acc, p0, n0, id, smem);
 #endif
 }
 
@@ -751,7 +750,7 @@ __global__ __launch_bounds__(64 * NW, (ST == 1 && MB * NB <= 16) ? 3 : 2) void c
 // unchanged; +0.9 % on the BA-update step in an interleaved A/B (950-956 -> 960-962 it/s).  The 256-channel tile (448 -> 256
 // 324 -> 363 us: 256 VGPRs with spills, the weights are two thirds of its staging anyway) and the 64-channel tile (43.7 ->
 // 47.8 us) lose and stay on conv_igemm_kernel; the dispatch takes this kernel for the 128-channel tile only.
-// Everything else is conv_igemm_kernel<EPI, 4, 64, 4, 1, MB>: same tile mapping, K order (chunk outermost, taps inside),
+// Everything else is conv_igemm_kernel<EPI, 4, 4>: same tile mapping, K order (chunk outermost, taps inside),
 // single LDS stage for the weights (wait, barrier, fragment reads, barrier, DMA of the next tile, MFMAs), same MFMA sequence
 // and epilogues - results are bit-identical (tests/test_gpu_update_op.py).  What differs:
 //   * zero padding moves from the DMA (bit 31 of a lane's offset) to the fragment: a lane whose pixel has no neighbour for
@@ -764,14 +763,14 @@ __global__ __launch_bounds__(64 * NW, (ST == 1 && MB * NB <= 16) ? 3 : 2) void c
 //     where the weights of the next tile are staged.  (Re-staging it in three parts as its rows go dead - the first W rows
 //     behind tap 2, the next W behind tap 5, the rest at the boundary - was measured: the step LOSES 2.6 %, 931-935 -> 907-910
 //     it/s; K-tiles that carry 14 pieces instead of 4 cost more than the one burst saves.)
-// LDS: weights 32 MB rows + 128 + 2 W + 2 pixel rows (the last DMA piece overlaps its predecessor so that the tile takes no
+// LDS: 128 weight rows + 128 + 2 W + 2 pixel rows (the last DMA piece overlaps its predecessor so that the tile takes no
 // more than that: 53.5 KB at W = 80, three workgroups per CU; with whole 8-row pieces it was two and 4 % slower than the
 // plain kernel); up to W = 83 for the 128-channel tile.
 // ------------------------------------------------------------------------------------------------------------------
-template <int EPI, int MB>
-__global__ __launch_bounds__(256, MB <= 4 ? 3 : 2) void conv_halo_kernel(ConvArgs a) {
+template <int EPI>
+__global__ __launch_bounds__(256, 3) void conv_halo_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int NB = 4, NW = 4, TN = 32 * MB, PT = 128, RB = 128, SL = 8, RPI = 8, KK = 2;
+  constexpr int MB = 4, NB = 4, NW = 4, TN = 32 * MB, PT = 128;
   constexpr int WI = TN / RPI / NW;                    // weight DMA instructions per wave per K-tile
   constexpr int WBYTES = TN * RB;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [weights][halo pixel rows]
@@ -783,34 +782,24 @@ __global__ __launch_bounds__(256, MB <= 4 ? 3 : 2) void conv_halo_kernel(ConvArg
   const int npieces = (hrows + RPI - 1) / RPI;         // DMA pieces of 8 rows
   char* const lx = smem + WBYTES;
 
-  const int nwg = gridDim.x, ntn = (a.nout + TN - 1) / TN;
-  const int xcd = blockIdx.x & 7, q = nwg >> 3, r = nwg & 7;
-  const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-  const int pt = lid / ntn, nt = lid - pt * ntn;
-  const int tpm = (a.HW + PT - 1) / PT;
-  const long p0 = EPI == EPI_GLO ? (long)(pt / tpm) * a.HW + (long)(pt % tpm) * PT : a.pbeg + (long)pt * PT;
-  const int n0 = nt * TN;
+  const TileId id = tile_id((a.nout + TN - 1) / TN);
+  const long p0 = a.pbeg + (long)id.pt * PT;
+  const int n0 = id.nt * TN;
   const int nchunks = a.cha + a.chb;
   const int C = nchunks * 64;
   const int T = 9 * nchunks;
 
   // descriptors `halo` rows in front of the tensors: halo row h of the tile is pixel p0 - halo + h
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.xa - (long)halo * a.xa_stride), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.xb - (long)halo * a.xb_stride), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x7fffffff, 0x00020000);
-  const int srow = lane / SL, slot = lane % SL;
-  const int row0 = wv * RPI + srow;
-  const int sw0 = (slot ^ (row0 & 7)) << 3;            // swizzled 16-byte slot, in halfs (key = row & 7 = srow)
-  const unsigned voffA0 = (unsigned)(((p0 + row0) * a.xa_stride + sw0) * 2);
-  const unsigned voffB0 = (unsigned)(((p0 + row0) * a.xb_stride + sw0) * 2);
-  const unsigned woff0 = (unsigned)(((size_t)row0 * C + sw0) * 2);
+  const __amdgpu_buffer_rsrc_t rA = conv_rsrc(a.xa, halo, a.xa_stride), rB = conv_rsrc(a.xb, halo, a.xb_stride);
+  const __amdgpu_buffer_rsrc_t rW = conv_rsrc(a.w);
+  const StageLane sl = stage_lane(lane, wv);
+  const unsigned voffA0 = stage_voff(sl, p0, a.xa_stride), voffB0 = stage_voff(sl, p0, a.xb_stride);
+  const unsigned woff0 = stage_woff(sl, C);
   constexpr int XIMAX = 12;                            // pieces per wave: ceil(ceil((128 + 2 W + 2) / 8) / 4), W <= 127
   unsigned hmask = 0;                                  // bit i: the row of piece i * 4 + wv this lane stages lies inside [0, P)
 #pragma unroll
   for (int i = 0; i < XIMAX; ++i) {
-    const long p = p0 - halo + (long)((i * NW + wv) * RPI + srow);
+    const long p = p0 - halo + (long)((i * NW + wv) * RPI + sl.srow);
     hmask |= (p >= 0 && p < a.P) ? (1u << i) : 0u;
   }
   auto stage_pixels = [&](int ch) {
@@ -831,10 +820,10 @@ __global__ __launch_bounds__(256, MB <= 4 ? 3 : 2) void conv_halo_kernel(ConvArg
       } else if (piece == npieces - 1) {
         // the last piece ends with the tile's last row (it re-writes up to 7 rows of its predecessor with the same bytes):
         // the tile then takes exactly 128 + 2 W + 2 rows of LDS, which is what lets three workgroups share a CU at W = 80
-        const int rowL = hrows - RPI + srow;
+        const int rowL = hrows - RPI + sl.srow;
         const long pL = p0 - halo + rowL;
         const unsigned invL = (pL >= 0 && pL < a.P) ? 0u : 0x80000000u;
-        const unsigned voL = invL | (unsigned)(((p0 + rowL) * xs + ((slot ^ (rowL & 7)) << 3)) * 2);
+        const unsigned voL = invL | (unsigned)(((p0 + rowL) * xs + ((sl.slot ^ (rowL & 7)) << 3)) * 2);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(segA ? rA : rB,
             (__attribute__((address_space(3))) void*)(lx + (hrows - RPI) * RB), 16, voL, xsoff, 0, 0);
       }
@@ -850,28 +839,15 @@ __global__ __launch_bounds__(256, MB <= 4 ? 3 : 2) void conv_halo_kernel(ConvArg
   };
 
   f32x4 acc[MB][NB];
-#pragma unroll
-  for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NB; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc);
 
   // tap validity of this lane's four pixels (blocks ni): bit 9 ni + d
   unsigned long long pmask = 0ull;
 #pragma unroll
-  for (int ni = 0; ni < NB; ++ni) {
-    const long p = p0 + wn * (16 * NB) + ni * 16 + col;
-    if (p < a.P) {
-      const int pi_ = (int)p, xw = pi_ % a.W, yh = (pi_ / a.W) % a.H;      // p < P < 2^31 (the 31-bit offset check of the launch)
-#pragma unroll
-      for (int d = 0; d < 9; ++d) {
-        const int dy = d / 3 - 1, dx = d % 3 - 1;
-        if ((unsigned)(yh + dy) < (unsigned)a.H && (unsigned)(xw + dx) < (unsigned)a.W) pmask |= 1ull << (9 * ni + d);
-      }
-    }
-  }
-  int woffr[KK];                                       // weight fragments: row = 16 blk + col, slot kk * 4 + kg, key = col & 7
-#pragma unroll
-  for (int kk = 0; kk < KK; ++kk) woffr[kk] = col * RB + (((kk * 4 + kg) ^ (col & 7)) << 4);
+  for (int ni = 0; ni < NB; ++ni)
+    pmask |= (unsigned long long)tap_mask(a, p0 + wn * (16 * NB) + ni * 16 + col, true) << (9 * ni);
+  int woffr[KK];                                       // weight fragments, read from the stage as in conv_igemm_kernel
+  frag_offsets(woffr, col, kg);
   const int wbase = wm * (16 * MB) * RB;
   const int rb0 = wn * (16 * NB) + col + halo;         // halo row of this lane's pixel of block 0 for the centre tap
 
@@ -919,32 +895,12 @@ __global__ __launch_bounds__(256, MB <= 4 ? 3 : 2) void conv_halo_kernel(ConvArg
       if (d1 == 0) stage_pixels(ch1);                  // the chunk's last tap has been read: its pixel rows are free
       stage_weights(ch1, d1);
     }
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-      for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NB; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kk][mi], xf[kk][ni], acc[mi][ni], 0, 0, 0);
+    mfma_tile(acc, wf, xf);
     ch = ch1;
     d = d1;
   }
 
-  if constexpr (EPI == EPI_GLO) {
-    if constexpr (MB == 4) conv_epilogue_glo<MB, NB>(a, acc, p0, p0 + wn * (16 * NB) + col, wm, wn, kg, col, smem, pt);
-  } else if constexpr (EPI == EPI_UPSAMPLE) {
-    if constexpr (MB == 4) conv_epilogue_upsample<MB, NB>(a, acc, p0, n0, wm, wn, kg, col, smem);
-  } else if constexpr (EPI == EPI_HEADS) {
-    if constexpr (MB == 4) {
-      if (nt < a.tap_groups)                                                    // workgroup-uniform
-        conv_epilogue_heads<MB, NB>(a, acc, p0, n0, wm, wn, kg, col, lane, smem);
-      else
-        conv_epilogue_tile<EPI_BIAS_ACT, MB, NB>(a, acc, p0 + wn * (16 * NB) + col, n0 + wm * (16 * MB) + kg * 4,
-                                                 a.tap_groups * 128);
-    }
-  } else {
-    conv_epilogue_tile<EPI, MB, NB>(a, acc, p0 + wn * (16 * NB) + col, n0 + wm * (16 * MB) + kg * 4);
-  }
+  conv_finish_tile<EPI>(a, acc, p0, n0, id, smem);
 #endif
 }
 
@@ -970,7 +926,7 @@ __global__ __launch_bounds__(256, MB <= 4 ? 3 : 2) void conv_halo_kernel(ConvArg
 //   * the DMA pieces are inline asm (m0 written in the same statement): hipcc drains every LDS-DMA it KNOWS of with
 //     vmcnt(0) before the next ds_read that might alias it, which would pin group 1's pieces to one phase of flight.
 // K order, MFMA sequence per accumulator, zero padding (bit 31 of the lane's offset) and the epilogues are those of
-// conv_igemm_kernel<EPI, 4, 64, 4, 1, 8>: the outputs are bit-identical (tests/test_gpu_update_op.py).
+// conv_igemm_kernel<EPI, 4, 8>: the outputs are bit-identical (tests/test_gpu_update_op.py).
 // The 128-CHANNEL layers (q gate, heads) were given the same schedule over a haloed pixel tile in two LDS buffers + three
 // weight stages (128 x 256 tile, wave tile 64 x 64, 157 KB; bit-identical on four shapes) and LOST to the haloed 128 x 128
 // tile at three workgroups per CU: q gate 151 vs 144 us, 128 -> 384 182 vs 157 us.  A phase then holds 32 MFMAs (~750-860
@@ -1007,16 +963,100 @@ __device__ __forceinline__ void dma16_masked_asm(__amdgpu_buffer_rsrc_t r, unsig
                                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   \
                                    __builtin_amdgcn_sched_barrier(0); } while (0)
 
+// ---- staging shared by the two ping-pong schedules (conv_pp_tile, conv_ppw_tile) ----
+// A group of four waves stages tiles of up to 256 rows: piece i of staging slot w4 = rows (i * 4 + w4) * RPI .. + RPI - 1.
+constexpr int PP_NWS = 4;                             // waves (staging slots) per group
+constexpr int PP_XBUF = 256 * RB;                     // one pixel buffer
+__device__ __forceinline__ unsigned lds_address(const char* smem) {
+  return (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
+}
+
+// K-tile t: 64-channel chunk t / taps (outermost), tap t % taps - the K order of conv_igemm_kernel
+struct PixTile { unsigned xsoff, xstep, l0, d; bool segA; };
+
+// Pixel staging of one wave: its XI pieces of the rows that start at pixel `first`, into the buffers of PP_XBUF bytes that
+// start at LDS address lds0 (which includes the wave's slot)
+template <int XI>
+struct PixStager {
+  __amdgpu_buffer_rsrc_t rA, rB;
+  unsigned voffA0, voffB0, lds0;
+  int back;
+  unsigned vmask[(XI + 2) / 3];                        // 9 tap bits per piece, three pieces per register
+
+  __device__ __forceinline__ PixStager(const ConvArgs& a, const StageLane& sl, int w4, long first, unsigned lds0_) {
+    back = tap_back(a);
+    rA = conv_rsrc(a.xa, back, a.xa_stride);
+    rB = conv_rsrc(a.xb, back, a.xb_stride);
+    voffA0 = stage_voff(sl, first, a.xa_stride);
+    voffB0 = stage_voff(sl, first, a.xb_stride);
+    lds0 = lds0_;
+#pragma unroll
+    for (int i = 0; i < (XI + 2) / 3; ++i) vmask[i] = 0;
+#pragma unroll
+    for (int i = 0; i < XI; ++i) vmask[i / 3] |= tap_mask(a, first + (i * PP_NWS + w4) * RPI + sl.srow) << (9 * (i % 3));
+  }
+  __device__ __forceinline__ PixTile tile(const ConvArgs& a, int t, int buf) const {
+    PixTile pt_;
+    const int ch = t / a.taps, d = t - ch * a.taps;
+    const int shift = (a.taps == 9 ? (d / 3 - 1) * a.W + (d % 3 - 1) : 0) + back;
+    pt_.segA = ch < a.cha;
+    const int xs = pt_.segA ? a.xa_stride : a.xb_stride;
+    pt_.xsoff = (unsigned)((shift * xs + (pt_.segA ? ch : ch - a.cha) * 64) * 2);
+    pt_.xstep = (unsigned)(PP_NWS * RPI * xs * 2);
+    pt_.l0 = lds0 + buf * PP_XBUF;
+    pt_.d = (unsigned)d;
+    return pt_;
+  }
+  __device__ __forceinline__ void pieces(const PixTile& pt_) const {
+#pragma unroll
+    for (int i = 0; i < XI; ++i)
+      dma16_masked_asm(pt_.segA ? rA : rB, pt_.segA ? voffA0 : voffB0, vmask[i / 3], pt_.d + 9 * (i % 3),
+                       pt_.xsoff + i * pt_.xstep, pt_.l0 + i * (PP_NWS * RPI * RB));
+  }
+};
+
+// Weight staging of one wave: its WI pieces of the TN weight rows of channel tile n0, into the stages of TN * RB bytes that
+// start at LDS address lds0 (which includes the wave's slot)
+template <int TN>
+struct WeightStager {
+  static constexpr int WI = TN / RPI / PP_NWS;
+  __amdgpu_buffer_rsrc_t rW;
+  unsigned woff0, wstep, lds0;
+  int n0, C;
+
+  __device__ __forceinline__ WeightStager(const ConvArgs& a, const StageLane& sl, int n0_, unsigned lds0_) {
+    C = (a.cha + a.chb) * 64;
+    rW = conv_rsrc(a.w);
+    woff0 = stage_woff(sl, C);
+    wstep = (unsigned)(PP_NWS * RPI * C * 2);
+    lds0 = lds0_;
+    n0 = n0_;
+  }
+  __device__ __forceinline__ void pieces(const ConvArgs& a, int t, int buf) const {
+    const int ch = t / a.taps, d = t - ch * a.taps;
+    const unsigned wsoff = (unsigned)((((size_t)d * a.npad + n0) * C + ch * 64) * 2);
+#pragma unroll
+    for (int i = 0; i < WI; ++i) dma16_asm(rW, woff0, wsoff + i * wstep, lds0 + buf * (TN * RB) + i * (PP_NWS * RPI * RB));
+  }
+};
+
+template <int MB, int NB>
+__device__ __forceinline__ void mfma_phase(f32x4 (&acc)[MB][NB], const f16x8 (&wf)[KK][MB], const f16x8 (&xf)[KK][NB]) {
+  __builtin_amdgcn_s_setprio(1);      // (no measurable effect: 225.5 us with, 227.4 without, 225.8 with the MEM phase raised instead)
+  mfma_tile(acc, wf, xf);
+  __builtin_amdgcn_s_setprio(0);
+}
+
 // (Round 6: the same wave tile on v_mfma_f32_32x32x16_f16 - 32 MFMAs per K-tile, MFMA phase 5-7 % shorter - was built and
 // removed: the 32 x 32 result layout doubles the epilogue's address work and the launch is 7-12 % slower,
 // profiles/r06_conv_m32.txt.)
 template <int EPI, int NB>
 __device__ __forceinline__ void conv_pp_tile(const ConvArgs& a, const long p0, const int n0, const int lid, char* smem) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int MB = 8, NWS = 4, TN = 256, PT = 64 * NB, RB = 128, SL = 8, RPI = 8, KK = 2;
-  constexpr int XI = PT / RPI / NWS, WI = TN / RPI / NWS;      // 8 pixel pieces per wave of group 0, 8 weight pieces per wave of group 1
-  constexpr int XBYTES = PT * RB, WBYTES = TN * RB;
-  constexpr int WBASE = 2 * 256 * RB;                           // LDS: pixel tiles 0 1 | weight tiles 0 1 2  (160 KB)
+  constexpr int MB = 8, TN = 256, PT = 64 * NB;
+  constexpr int XI = PT / RPI / PP_NWS;                         // 8 pixel pieces per wave of group 0 (and 8 weight pieces per wave of group 1)
+  constexpr int WBYTES = TN * RB;
+  constexpr int WBASE = 2 * PP_XBUF;                            // LDS: pixel tiles 0 1 | weight tiles 0 1 2  (160 KB)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int w4 = wv & 3;                                        // staging slot inside the group
@@ -1024,18 +1064,12 @@ __device__ __forceinline__ void conv_pp_tile(const ConvArgs& a, const long p0, c
   const int wm = wv & 1, wn = wv >> 1;
   const int grp = wv >> 2;                                      // waves w and w + 4 share a SIMD
 
-  const int nchunks = a.cha + a.chb;
-  const int C = nchunks * 64;
-  const int T = a.taps * nchunks;
+  const int T = a.taps * (a.cha + a.chb);
 
   f32x4 acc[MB][NB];
-#pragma unroll
-  for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NB; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc);
   int foff[KK];
-#pragma unroll
-  for (int kk = 0; kk < KK; ++kk) foff[kk] = col * RB + (((kk * 4 + kg) ^ (col & 7)) << 4);
+  frag_offsets(foff, col, kg);
   const int wfrag = WBASE + wm * (16 * MB) * RB, xfrag = wn * (16 * NB) * RB;
   f16x8 wf[KK][MB], xf[KK][NB];
 
@@ -1044,44 +1078,13 @@ __device__ __forceinline__ void conv_pp_tile(const ConvArgs& a, const long p0, c
   // phase against 1404 with the pieces first and 1164 with the reads first, tools/conv_pp_timeline.sh).  Across waves they
   // do: staging slots 0 / 1 read first, slots 2 / 3 issue their pieces first, so the LDS pipe and the address unit both have
   // work during the whole phase.
-  auto read_frags = [&](int xb, int wb) {
-    const char* bx = smem + xb * (256 * RB) + xfrag;
-    const char* bw = smem + wb * WBYTES + wfrag;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-#pragma unroll
-      for (int mi = 0; mi < MB; ++mi) wf[kk][mi] = *reinterpret_cast<const f16x8*>(bw + mi * 16 * RB + foff[kk]);
-#pragma unroll
-      for (int ni = 0; ni < NB; ++ni) xf[kk][ni] = *reinterpret_cast<const f16x8*>(bx + ni * 16 * RB + foff[kk]);
-    }
-  };
+  auto frags = [&](int xb, int wb) { read_frags(wf, xf, smem + wb * WBYTES + wfrag, smem + xb * PP_XBUF + xfrag, foff); };
   const bool pieces_first = w4 >= 2;
-  auto mfmas = [&]() {
-    __builtin_amdgcn_s_setprio(1);      // (no measurable effect here: 225.5 us with, 227.4 without, 225.8 with the MEM phase raised instead)
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-      for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NB; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kk][mi], xf[kk][ni], acc[mi][ni], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
 
-#ifdef EXP_CONV_STAMPS
-  // experiment (tools/conv_pp_timeline.py): shader-clock stamps of K-tiles 10-13 of every 41st workgroup, [16][8][4][4]
-  const int swg = lid / 41;
-#define PP_STAMP(k) do { if (a.stamps && lane == 0 && lid >= 0 && lid % 41 == 0 && swg < 16 && t >= 10 && t < 14) { unsigned long long ts_; \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts_) : : "memory");                                              \
-    a.stamps[((swg * NW + wv) * 4 + (t - 10)) * 4 + (k)] = ts_; } } while (0)
-#else
-#define PP_STAMP(k)
-#endif
-  const int srow = lane / SL, slot = lane % SL;
-  const int row0 = w4 * RPI + srow;                             // piece i of staging slot w4: rows (i * NWS + w4) * RPI .. + RPI - 1
-  const int sw0 = (slot ^ (row0 & 7)) << 3;
-  const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem) + (unsigned)(w4 * RPI * RB);
-  // K-tile t: 64-channel chunk t / taps (outermost), tap t % taps - the K order of conv_igemm_kernel
+  // experiment (tools/conv_pp_timeline.py): stamps of every 41st workgroup with a full tile, [16][8][4][4]
+#define PP_STAMP(k) CONV_STAMP(lid, 41, 8, 4, k)
+  const StageLane sl = stage_lane(lane, w4);
+  const unsigned lds0 = lds_address(smem) + (unsigned)(w4 * RPI * RB);
 
   // barrier k = the k-th workgroup barrier; group 0: MEM(t) between barriers 2t and 2t + 1, MFMA(t) between 2t + 1 and
   // 2t + 2; group 1 one barrier later (MEM(t) in the odd period 2t + 1).
@@ -1090,127 +1093,48 @@ __device__ __forceinline__ void conv_pp_tile(const ConvArgs& a, const long p0, c
   //   weight tile t + 2 -> stage (t + 2) % 3, free behind barrier 2t (ditto), due at barrier 2t + 4: group 1 in its MEM(t)
   //     phase (period 2t + 1) behind its fragment reads; it waits for tile t + 1 there with vmcnt(8) - three periods of flight.
   if (grp == 0) {
-    const int back = a.taps == 9 ? a.W + 1 : 0;
-    const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.xa - (long)back * a.xa_stride), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.xb - (long)back * a.xb_stride), 0, 0x7fffffff, 0x00020000);
-    const unsigned voffA0 = (unsigned)(((p0 + row0) * a.xa_stride + sw0) * 2);
-    const unsigned voffB0 = (unsigned)(((p0 + row0) * a.xb_stride + sw0) * 2);
-    unsigned vmask[(XI + 2) / 3];                        // 9 tap bits per piece, three pieces per register
-#pragma unroll
-    for (int i = 0; i < (XI + 2) / 3; ++i) vmask[i] = 0;
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-      const long p = p0 + (i * NWS + w4) * RPI + srow;
-      unsigned m = 0;
-      if (p < a.P) {
-        const int pi_ = (int)p, xw = pi_ % a.W, yh = (pi_ / a.W) % a.H;
-        if (a.taps == 9) {
-#pragma unroll
-          for (int d = 0; d < 9; ++d) {
-            const int dy = d / 3 - 1, dx = d % 3 - 1;
-            if ((unsigned)(yh + dy) < (unsigned)a.H && (unsigned)(xw + dx) < (unsigned)a.W) m |= 1u << d;
-          }
-        } else {
-          m = 1;
-        }
-      }
-      vmask[i / 3] |= m << (9 * (i % 3));
-    }
-    struct PixTile { unsigned xsoff, xstep, l0, d; bool segA; };
-    auto pix_tile = [&](int t, int buf) {
-      PixTile pt_;
-      const int ch = t / a.taps, d = t - ch * a.taps;
-      const int shift = (a.taps == 9 ? (d / 3 - 1) * a.W + (d % 3 - 1) : 0) + back;
-      pt_.segA = ch < a.cha;
-      const int xs = pt_.segA ? a.xa_stride : a.xb_stride;
-      pt_.xsoff = (unsigned)((shift * xs + (pt_.segA ? ch : ch - a.cha) * 64) * 2);
-      pt_.xstep = (unsigned)(NWS * RPI * xs * 2);
-      pt_.l0 = lds0 + buf * (256 * RB);
-      pt_.d = (unsigned)d;
-      return pt_;
-    };
-    auto pix_piece = [&](const PixTile& pt_, int i) {
-      dma16_masked_asm(pt_.segA ? rA : rB, pt_.segA ? voffA0 : voffB0, vmask[i / 3], pt_.d + 9 * (i % 3),
-                       pt_.xsoff + i * pt_.xstep, pt_.l0 + i * (NWS * RPI * RB));
-    };
-    {
-      const PixTile p0_ = pix_tile(0, 0);
-#pragma unroll
-      for (int i = 0; i < XI; ++i) pix_piece(p0_, i);
-    }
+    const PixStager<XI> px(a, sl, w4, p0, lds0);
+    px.pieces(px.tile(a, 0, 0));
     for (int t = 0; t < T; ++t) {
       PP_WAIT_VM_BARRIER();                               // barrier 2t: pixel tile t landed (own pieces), weight tile t: group 1
       PP_STAMP(0);
-#ifdef EXP_PP_NO_PIECES
-      const bool more = false;                            // ablation (wrong results): no DMA in the K loop
-#else
       const bool more = t + 1 < T;
-#endif
-      const PixTile nx = pix_tile(more ? t + 1 : 0, (t + 1) & 1);
+      const PixTile nx = px.tile(a, more ? t + 1 : 0, (t + 1) & 1);
       if (pieces_first) {
-        if (more) {
-#pragma unroll
-          for (int i = 0; i < XI; ++i) pix_piece(nx, i);
-        }
+        if (more) px.pieces(nx);
         __builtin_amdgcn_sched_barrier(0);
-        read_frags(t & 1, t % 3);
+        frags(t & 1, t % 3);
       } else {
-        read_frags(t & 1, t % 3);
+        frags(t & 1, t % 3);
         __builtin_amdgcn_sched_barrier(0);
-        if (more) {
-#pragma unroll
-          for (int i = 0; i < XI; ++i) pix_piece(nx, i);
-        }
+        if (more) px.pieces(nx);
       }
       PP_STAMP(3);
       PP_WAIT_LGKM_BARRIER();                             // barrier 2t + 1
       PP_STAMP(1);
-      mfmas();
+      mfma_phase(acc, wf, xf);
       PP_STAMP(2);
     }
     PP_BARRIER();                                         // barrier 2T (group 1's last one)
   } else {
-    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x7fffffff, 0x00020000);
-    const unsigned woff0 = (unsigned)(((size_t)row0 * C + sw0) * 2);
-    const unsigned wstep = (unsigned)(NWS * RPI * C * 2);
-    auto w_piece = [&](int t, int buf, int i) {
-      const int ch = t / a.taps, d = t - ch * a.taps;
-      const unsigned wsoff = (unsigned)((((size_t)d * a.npad + n0) * C + ch * 64) * 2);
-      dma16_asm(rW, woff0, wsoff + i * wstep, lds0 + WBASE + buf * WBYTES + i * (NWS * RPI * RB));
-    };
-#pragma unroll
-    for (int i = 0; i < WI; ++i) w_piece(0, 0, i);
-    if (1 < T) {
-#pragma unroll
-      for (int i = 0; i < WI; ++i) w_piece(1, 1, i);
-    }
+    const WeightStager<TN> ws(a, sl, n0, lds0 + WBASE);
+    ws.pieces(a, 0, 0);
+    if (1 < T) ws.pieces(a, 1, 1);
     PP_WAIT_VM_BARRIER();                                 // barrier 0: weight tiles 0 and 1 landed
     int wb = 0;                                           // t % 3
     for (int t = 0; t < T; ++t) {
       PP_BARRIER();                                       // barrier 2t + 1
       PP_STAMP(0);
-#ifdef EXP_PP_NO_PIECES
-      const bool more = false;
-#else
       const bool more = t + 2 < T;
-#endif
       const int wnext = wb == 0 ? 2 : wb - 1;             // (t + 2) % 3
       if (pieces_first) {
-        if (more) {
-#pragma unroll
-          for (int i = 0; i < WI; ++i) w_piece(t + 2, wnext, i);
-        }
+        if (more) ws.pieces(a, t + 2, wnext);
         __builtin_amdgcn_sched_barrier(0);
-        read_frags(t & 1, wb);
+        frags(t & 1, wb);
       } else {
-        read_frags(t & 1, wb);
+        frags(t & 1, wb);
         __builtin_amdgcn_sched_barrier(0);
-        if (more) {
-#pragma unroll
-          for (int i = 0; i < WI; ++i) w_piece(t + 2, wnext, i);
-        }
+        if (more) ws.pieces(a, t + 2, wnext);
       }
       PP_STAMP(3);
       __builtin_amdgcn_sched_barrier(0);
@@ -1218,11 +1142,12 @@ __device__ __forceinline__ void conv_pp_tile(const ConvArgs& a, const long p0, c
       else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
       PP_STAMP(1);
-      mfmas();
+      mfma_phase(acc, wf, xf);
       PP_STAMP(2);
       wb = wb == 2 ? 0 : wb + 1;
     }
   }
+#undef PP_STAMP
   conv_epilogue_tile<EPI, MB, NB>(a, acc, p0 + wn * (16 * NB) + col, n0 + wm * (16 * MB) + kg * 4);
 #endif
 }
@@ -1236,17 +1161,12 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ntn = a.nout / 256;
-  const int bid = blockIdx.x, nfull = a.pp_full;
-  const bool full = bid < nfull;
-  const int base = full ? 0 : nfull, nwg = full ? nfull : (int)gridDim.x - nfull, j = bid - base;
-  const int xcd = j & 7, q = nwg >> 3, r = nwg & 7;
-  const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (j >> 3);
-  const int pt = lid / ntn, nt = lid - pt * ntn;
-  const int n0 = nt * 256;
-  if (full) {
-    conv_pp_tile<EPI, 4>(a, (long)pt * 256, n0, lid, smem);
+  const TileId id = tile_id(ntn, a.pp_full);
+  const int n0 = id.nt * 256;
+  if (id.full) {
+    conv_pp_tile<EPI, 4>(a, (long)id.pt * 256, n0, id.lid, smem);
   } else {
-    const long p0 = (long)(nfull / ntn) * 256 + (long)pt * (64 * a.pp_nbr);
+    const long p0 = (long)(a.pp_full / ntn) * 256 + (long)id.pt * (64 * a.pp_nbr);
     if (a.pp_nbr == 3) conv_pp_tile<EPI, 3>(a, p0, n0, -1, smem);
     else if (a.pp_nbr == 2) conv_pp_tile<EPI, 2>(a, p0, n0, -1, smem);
     else conv_pp_tile<EPI, 1>(a, p0, n0, -1, smem);
@@ -1266,7 +1186,7 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(ConvArgs a) {
 //     MEM phase of tile t - 1; 8 pieces per wave), waited for with vmcnt(0) at the end of its MFMA phase - two periods of flight;
 //   group 0 additionally stages the weight tile t + 1 (4 pieces per wave) into stage (t + 1) & 1, whose last reader (group 1,
 //     tile t - 1, period 2t - 1) retired its reads in front of barrier 2t; group 1 reads it three barriers later.
-// K order, MFMA sequence per accumulator, zero padding and epilogues are those of conv_igemm_kernel<EPI, 4, 64, 4, 1, 4>:
+// K order, MFMA sequence per accumulator, zero padding and epilogues are those of conv_igemm_kernel<EPI, 4, 4>:
 // bit-identical outputs (tests/test_gpu_update_op.py::test_conv_wide_pingpong_tiles_are_bit_identical).  The heads' tap GEMM
 // needs no LDS here: a wave holds all 128 hidden channels of its 64 pixels (the two 64-channel halves are summed in registers
 // in the order the 128 x 128 tile sums them through LDS).
@@ -1319,163 +1239,66 @@ __device__ __forceinline__ void conv_epilogue_heads_w(const ConvArgs& a, f32x4 (
 template <int EPI, int NB>
 __device__ __forceinline__ void conv_ppw_tile(const ConvArgs& a, const long p0, const int n0, const int nt, char* smem) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int MB = 8, NWS = 4, RB = 128, SL = 8, RPI = 8, KK = 2;
+  constexpr int MB = 8, TN = 128;
   constexpr int PG = 64 * NB;                                   // pixel rows of one group's half of the tile
-  constexpr int XI = PG / RPI / NWS, WI = 128 / RPI / NWS;      // 2 NB pixel pieces per wave; 4 weight pieces per wave of group 0
-  constexpr int XBUF = 256 * RB;                                // one pixel buffer, [group][buffer]
-  constexpr int WBASE = 4 * XBUF, WBYTES = 128 * RB;            // weight stages 0 1 behind the four pixel buffers (160 KB)
+  constexpr int XI = PG / RPI / PP_NWS;                         // 2 NB pixel pieces per wave (and 4 weight pieces per wave of group 0)
+  constexpr int WBASE = 4 * PP_XBUF, WBYTES = TN * RB;          // pixel buffers [group][buffer], weight stages 0 1 behind them (160 KB)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int w4 = wv & 3;                                        // staging slot inside the group = pixel quarter of its half
   const int col = lane & 15, kg = lane >> 4;
   const int grp = wv >> 2;                                      // waves w and w + 4 share a SIMD
 
-  const int nchunks = a.cha + a.chb;
-  const int C = nchunks * 64;
-  const int T = a.taps * nchunks;
+  const int T = a.taps * (a.cha + a.chb);
 
   f32x4 acc[MB][NB];
-#pragma unroll
-  for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NB; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+  clear_acc(acc);
   int foff[KK];
-#pragma unroll
-  for (int kk = 0; kk < KK; ++kk) foff[kk] = col * RB + (((kk * 4 + kg) ^ (col & 7)) << 4);
-  const int xfrag = grp * 2 * XBUF + w4 * (16 * NB) * RB;
+  frag_offsets(foff, col, kg);
+  const int xfrag = grp * 2 * PP_XBUF + w4 * (16 * NB) * RB;
   f16x8 wf[KK][MB], xf[KK][NB];
 
-  auto read_frags = [&](int buf) {                              // pixel buffer and weight stage of tile t: both t & 1
-    const char* bx = smem + xfrag + buf * XBUF;
-    const char* bw = smem + WBASE + buf * WBYTES;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-#pragma unroll
-      for (int mi = 0; mi < MB; ++mi) wf[kk][mi] = *reinterpret_cast<const f16x8*>(bw + mi * 16 * RB + foff[kk]);
-#pragma unroll
-      for (int ni = 0; ni < NB; ++ni) xf[kk][ni] = *reinterpret_cast<const f16x8*>(bx + ni * 16 * RB + foff[kk]);
-    }
+  auto frags = [&](int buf) {                                   // pixel buffer and weight stage of tile t: both t & 1
+    read_frags(wf, xf, smem + WBASE + buf * WBYTES, smem + xfrag + buf * PP_XBUF, foff);
   };
   const bool pieces_first = w4 >= 2;                            // (conv_pp_tile: the LDS pipe and the address unit both stay busy)
-  auto mfmas = [&]() {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk)
-#pragma unroll
-      for (int mi = 0; mi < MB; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NB; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kk][mi], xf[kk][ni], acc[mi][ni], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
 
-  const int srow = lane / SL, slot = lane % SL;
-  const int row0 = w4 * RPI + srow;                             // piece i of staging slot w4: rows (i * NWS + w4) * RPI .. + RPI - 1
-  const int sw0 = (slot ^ (row0 & 7)) << 3;
-  const unsigned ldsb = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);
-  const unsigned lds0 = ldsb + (unsigned)(grp * 2 * XBUF + w4 * RPI * RB);
-  const long ph = p0 + (long)grp * PG;                          // first pixel of this group's half
-
-  // ---- pixel staging of this wave's group (both groups) ----
-  const int back = a.taps == 9 ? a.W + 1 : 0;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.xa - (long)back * a.xa_stride), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(a.xb - (long)back * a.xb_stride), 0, 0x7fffffff, 0x00020000);
-  const unsigned voffA0 = (unsigned)(((ph + row0) * a.xa_stride + sw0) * 2);
-  const unsigned voffB0 = (unsigned)(((ph + row0) * a.xb_stride + sw0) * 2);
-  unsigned vmask[(XI + 2) / 3];                                 // 9 tap bits per piece, three pieces per register
-#pragma unroll
-  for (int i = 0; i < (XI + 2) / 3; ++i) vmask[i] = 0;
-#pragma unroll
-  for (int i = 0; i < XI; ++i) {
-    const long p = ph + (i * NWS + w4) * RPI + srow;
-    unsigned m = 0;
-    if (p < a.P) {
-      const int pi_ = (int)p, xw = pi_ % a.W, yh = (pi_ / a.W) % a.H;
-      if (a.taps == 9) {
-#pragma unroll
-        for (int d = 0; d < 9; ++d) {
-          const int dy = d / 3 - 1, dx = d % 3 - 1;
-          if ((unsigned)(yh + dy) < (unsigned)a.H && (unsigned)(xw + dx) < (unsigned)a.W) m |= 1u << d;
-        }
-      } else {
-        m = 1;
-      }
-    }
-    vmask[i / 3] |= m << (9 * (i % 3));
-  }
-  struct PixTile { unsigned xsoff, xstep, l0, d; bool segA; };
-  auto pix_tile = [&](int t, int buf) {
-    PixTile pt_;
-    const int ch = t / a.taps, d = t - ch * a.taps;
-    const int shift = (a.taps == 9 ? (d / 3 - 1) * a.W + (d % 3 - 1) : 0) + back;
-    pt_.segA = ch < a.cha;
-    const int xs = pt_.segA ? a.xa_stride : a.xb_stride;
-    pt_.xsoff = (unsigned)((shift * xs + (pt_.segA ? ch : ch - a.cha) * 64) * 2);
-    pt_.xstep = (unsigned)(NWS * RPI * xs * 2);
-    pt_.l0 = lds0 + buf * XBUF;
-    pt_.d = (unsigned)d;
-    return pt_;
-  };
-  auto pix_piece = [&](const PixTile& pt_, int i) {
-    dma16_masked_asm(pt_.segA ? rA : rB, pt_.segA ? voffA0 : voffB0, vmask[i / 3], pt_.d + 9 * (i % 3),
-                     pt_.xsoff + i * pt_.xstep, pt_.l0 + i * (NWS * RPI * RB));
-  };
-  // ---- weight staging (group 0) ----
-  const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, 0x7fffffff, 0x00020000);
-  const unsigned woff0 = (unsigned)(((size_t)row0 * C + sw0) * 2);
-  const unsigned wstep = (unsigned)(NWS * RPI * C * 2);
-  const unsigned ldsw0 = ldsb + (unsigned)(WBASE + w4 * RPI * RB);
-  auto w_piece = [&](int t, int buf, int i) {
-    const int ch = t / a.taps, d = t - ch * a.taps;
-    const unsigned wsoff = (unsigned)((((size_t)d * a.npad + n0) * C + ch * 64) * 2);
-    dma16_asm(rW, woff0, wsoff + i * wstep, ldsw0 + buf * WBYTES + i * (NWS * RPI * RB));
-  };
+  const StageLane sl = stage_lane(lane, w4);
+  const unsigned ldsb = lds_address(smem);
+  // every wave stages the pixels of its group's half; the waves of group 0 the weights as well
+  const PixStager<XI> px(a, sl, w4, p0 + (long)grp * PG, ldsb + (unsigned)(grp * 2 * PP_XBUF + w4 * RPI * RB));
+  const WeightStager<TN> ws(a, sl, n0, ldsb + (unsigned)(WBASE + w4 * RPI * RB));
 
   // barrier k = the k-th workgroup barrier; group 0: MEM(t) between barriers 2t and 2t + 1, MFMA(t) between 2t + 1 and 2t + 2;
   // group 1 one barrier later.  Every wave waits vmcnt(0) in front of the barrier that opens its MEM phase (its own pieces of
   // the tile it is about to read - and, for group 0, the weight tile both groups are about to read - have landed).
-  {
-    const PixTile p0_ = pix_tile(0, 0);
-#pragma unroll
-    for (int i = 0; i < XI; ++i) pix_piece(p0_, i);
-  }
+  px.pieces(px.tile(a, 0, 0));
   if (grp == 0) {
-#pragma unroll
-    for (int i = 0; i < WI; ++i) w_piece(0, 0, i);
+    ws.pieces(a, 0, 0);
   } else {
     PP_WAIT_VM_BARRIER();                                 // barrier 0
   }
   for (int t = 0; t < T; ++t) {
     PP_WAIT_VM_BARRIER();                                 // group 0: barrier 2t; group 1: barrier 2t + 1
     const bool more = t + 1 < T;
-    const PixTile nx = pix_tile(more ? t + 1 : 0, (t + 1) & 1);
+    const PixTile nx = px.tile(a, more ? t + 1 : 0, (t + 1) & 1);
     if (pieces_first) {
       if (more) {
-#pragma unroll
-        for (int i = 0; i < XI; ++i) pix_piece(nx, i);
-        if (grp == 0) {
-#pragma unroll
-          for (int i = 0; i < WI; ++i) w_piece(t + 1, (t + 1) & 1, i);
-        }
+        px.pieces(nx);
+        if (grp == 0) ws.pieces(a, t + 1, (t + 1) & 1);
       }
       __builtin_amdgcn_sched_barrier(0);
-      read_frags(t & 1);
+      frags(t & 1);
     } else {
-      read_frags(t & 1);
+      frags(t & 1);
       __builtin_amdgcn_sched_barrier(0);
       if (more) {
-#pragma unroll
-        for (int i = 0; i < XI; ++i) pix_piece(nx, i);
-        if (grp == 0) {
-#pragma unroll
-          for (int i = 0; i < WI; ++i) w_piece(t + 1, (t + 1) & 1, i);
-        }
+        px.pieces(nx);
+        if (grp == 0) ws.pieces(a, t + 1, (t + 1) & 1);
       }
     }
     PP_WAIT_LGKM_BARRIER();                               // group 0: barrier 2t + 1; group 1: barrier 2t + 2
-    mfmas();
+    mfma_phase(acc, wf, xf);
   }
   if (grp == 0) PP_BARRIER();                             // barrier 2T (group 1's last one)
 
@@ -1498,202 +1321,144 @@ __global__ __launch_bounds__(512, 1) void conv_ppw_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int ntn = a.nout / 128;
-  const int bid = blockIdx.x, nfull = a.pp_full;
-  const bool full = bid < nfull;
-  const int base = full ? 0 : nfull, nwg = full ? nfull : (int)gridDim.x - nfull, j = bid - base;
-  const int xcd = j & 7, q = nwg >> 3, r = nwg & 7;
-  const int lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (j >> 3);
-  const int pt = lid / ntn, nt = lid - pt * ntn;
-  const int n0 = nt * 128;
-  if (full) {
-    conv_ppw_tile<EPI, 4>(a, (long)pt * 512, n0, nt, smem);
+  const TileId id = tile_id(ntn, a.pp_full);
+  const int n0 = id.nt * 128;
+  if (id.full) {
+    conv_ppw_tile<EPI, 4>(a, (long)id.pt * 512, n0, id.nt, smem);
   } else {
-    const long p0 = (long)(nfull / ntn) * 512 + (long)pt * (128 * a.pp_nbr);
-    if (a.pp_nbr == 3) conv_ppw_tile<EPI, 3>(a, p0, n0, nt, smem);
-    else if (a.pp_nbr == 2) conv_ppw_tile<EPI, 2>(a, p0, n0, nt, smem);
-    else conv_ppw_tile<EPI, 1>(a, p0, n0, nt, smem);
+    const long p0 = (long)(a.pp_full / ntn) * 512 + (long)id.pt * (128 * a.pp_nbr);
+    if (a.pp_nbr == 3) conv_ppw_tile<EPI, 3>(a, p0, n0, id.nt, smem);
+    else if (a.pp_nbr == 2) conv_ppw_tile<EPI, 2>(a, p0, n0, id.nt, smem);
+    else conv_ppw_tile<EPI, 1>(a, p0, n0, id.nt, smem);
   }
 #endif
 }
 
-template <int EPI, int NB, int BK, int NW, int ST, int MB>
-static void launch_one(const ConvArgs& a, dim3 grid, hipStream_t st) {
-  constexpr int RB = BK * 2, PT = (NW / 2) * 16 * NB;
-  constexpr size_t stage_bytes = (size_t)ST * (PT * RB + 32 * MB * RB);
-  constexpr size_t lds = stage_bytes;
-  static PerDeviceOnce attr;            // > 64 KB of dynamic LDS needs the opt-in once per kernel
-  if (attr.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<EPI, NB, BK, NW, ST, MB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
-  hipLaunchKernelGGL((conv_igemm_kernel<EPI, NB, BK, NW, ST, MB>), grid, dim3(64 * NW), lds, st, a);
-}
-
-template <int EPI, int MB>
-static void launch_halo_one(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t st) {
-  static size_t granted[kMaxDevices] = {};    // more dynamic LDS than 64 KB needs the opt-in (per kernel, device and size)
+// Launch of any of the kernels.  More than 64 KB of dynamic LDS needs the opt-in per kernel and device; it is renewed whenever
+// a launch asks for more than was granted so far (conv_halo_kernel's LDS grows with the image width)
+template <auto Kernel>
+static void launch_kernel(const ConvArgs& a, dim3 grid, int threads, size_t lds, hipStream_t st) {
+  static size_t granted[kMaxDevices] = {};
   size_t& g = granted[current_device()];
   if (lds > 64 * 1024 && lds > g) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_halo_kernel<EPI, MB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     g = lds;
   }
-  hipLaunchKernelGGL((conv_halo_kernel<EPI, MB>), grid, dim3(256), lds, st, a);
+  hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, st, a);
 }
-// LDS of conv_halo_kernel: weight stage + haloed pixel rows, and never less than the
-// [pixel][channel] tile its seeding prologue / epilogues lay out
-static size_t halo_lds_bytes(int W, int MB) {
-  const size_t need = (size_t)32 * MB * 128 + (size_t)(128 + 2 * (W + 1)) * 128;
-  const size_t seed = (size_t)128 * 32 * MB * 2;
-  return need > seed ? need : seed;
-}
-template <int EPI>
-static void launch_pp_one(const ConvArgs& a, dim3 grid, hipStream_t st) {
-  constexpr size_t lds = 5 * 256 * 128;                     // two pixel stages + three weight stages
-  static PerDeviceOnce attr;
-  if (attr.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pp_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  }
-  hipLaunchKernelGGL((conv_pp_kernel<EPI>), grid, dim3(512), lds, st, a);
-}
-// 256-channel x 256-pixel ping-pong tiles (conv_pp_kernel): layers whose output channels are a multiple of 256
-static int launch_conv_pp(const ConvArgs& a_, int epilogue, hipStream_t st) {
-  if ((a_.nout & 255) || a_.pbeg != 0) return GLORIE_EUNSUPPORTED;
-  ConvArgs a = a_;
+
+// Tile plan of the ping-pong kernels, tiles of tn channels x full_px pixels: whole rounds of full tiles (one workgroup per CU,
+// `ntn` channel tiles per pixel tile); what is left goes into one partial round of smaller tiles (nbr sub-blocks of
+// full_px / 4 pixels) when that makes the round shorter.  Sets a.pp_full and a.pp_nbr, returns the workgroups of the launch
+static long plan_pp_tiles(ConvArgs& a, int tn, int full_px) {
+  const int sub_px = full_px / 4;
   const int ncu = device_cus();
-  const long ntn = a.nout / 256;
-  const long pt_all = (a.P + 255) / 256;
-  // whole rounds of full tiles (one workgroup per CU, `ntn` channel tiles per pixel tile); what is left goes into one partial
-  // round of smaller tiles when that makes the round shorter
+  const long ntn = a.nout / tn;
+  const long pt_all = (a.P + full_px - 1) / full_px;
   long full_pt = pt_all * ntn / ncu * ncu / ntn;
   full_pt -= full_pt % 8;                                   // (the XCD remap of both ranges wants multiples of 8)
   if (full_pt < 0) full_pt = 0;
-  long rest_px = a.P - full_pt * 256;
+  const long rest_px = a.P - full_pt * full_px;
   int nbr = 4;
   long rest_pt = 0;
   if (rest_px > 0) {
     const long per_cu = (rest_px * ntn + ncu - 1) / ncu;    // pixels per CU if the rest is spread evenly
-    nbr = (int)((per_cu + 63) / 64);
+    nbr = (int)((per_cu + sub_px - 1) / sub_px);
     if (nbr > 4 || full_pt == 0) nbr = 4;
     if (nbr < 1) nbr = 1;
-    rest_pt = (rest_px + 64 * nbr - 1) / (64 * nbr);
+    rest_pt = (rest_px + sub_px * nbr - 1) / (sub_px * nbr);
   }
   if (nbr == 4) { full_pt = pt_all; rest_pt = 0; }
-  const long nwg = (full_pt + rest_pt) * ntn;
-  if (nwg <= 0) return GLORIE_OK;
-  if (nwg > 0x7fffffffL) return GLORIE_EINVAL;
   a.pp_full = (int)(full_pt * ntn);
   a.pp_nbr = nbr;
+  return (full_pt + rest_pt) * ntn;
+}
+
+// 256-channel x 256-pixel ping-pong tiles (conv_pp_kernel): layers whose output channels are a multiple of 256
+static int launch_conv_pp(const ConvArgs& a_, int epilogue, hipStream_t st) {
+  if ((a_.nout & 255) || a_.pbeg != 0) return GLORIE_EUNSUPPORTED;
+  ConvArgs a = a_;
+  const long nwg = plan_pp_tiles(a, 256, 256);
+  if (nwg <= 0) return GLORIE_OK;
+  if (nwg > 0x7fffffffL) return GLORIE_EINVAL;
   const dim3 grid((unsigned)nwg);
+  constexpr size_t lds = 5 * 256 * 128;                     // two pixel stages + three weight stages
   switch (epilogue) {
-    case EPI_BIAS_ACT: launch_pp_one<EPI_BIAS_ACT>(a, grid, st); break;
-    case EPI_GRU_ZR: launch_pp_one<EPI_GRU_ZR>(a, grid, st); break;
+    case EPI_BIAS_ACT: launch_kernel<conv_pp_kernel<EPI_BIAS_ACT>>(a, grid, 512, lds, st); break;
+    case EPI_GRU_ZR: launch_kernel<conv_pp_kernel<EPI_GRU_ZR>>(a, grid, 512, lds, st); break;
     default: return GLORIE_EUNSUPPORTED;
   }
   return check_launch();
 }
 
-template <int EPI>
-static void launch_ppw_one(const ConvArgs& a, dim3 grid, hipStream_t st) {
-  constexpr size_t lds = 4 * 256 * 128 + 2 * 128 * 128;     // four pixel buffers + two weight stages = 160 KB
-  static PerDeviceOnce attr;
-  if (attr.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ppw_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-  }
-  hipLaunchKernelGGL((conv_ppw_kernel<EPI>), grid, dim3(512), lds, st, a);
-}
 // 128-channel x 512-pixel ping-pong tiles (conv_ppw_kernel): layers whose output channels are a multiple of 128
 static int launch_conv_ppw(const ConvArgs& a_, int epilogue, hipStream_t st) {
   if ((a_.nout & 127) || a_.pbeg != 0) return GLORIE_EUNSUPPORTED;
   ConvArgs a = a_;
-  const int ncu = device_cus();
-  const long ntn = a.nout / 128;
-  const long pt_all = (a.P + 511) / 512;
-  // whole rounds of full tiles, the rest in one partial round of smaller tiles when that makes the round shorter (launch_conv_pp)
-  long full_pt = pt_all * ntn / ncu * ncu / ntn;
-  full_pt -= full_pt % 8;
-  if (full_pt < 0) full_pt = 0;
-  long rest_px = a.P - full_pt * 512;
-  int nbr = 4;
-  long rest_pt = 0;
-  if (rest_px > 0) {
-    const long per_cu = (rest_px * ntn + ncu - 1) / ncu;
-    nbr = (int)((per_cu + 127) / 128);
-    if (nbr > 4 || full_pt == 0) nbr = 4;
-    if (nbr < 1) nbr = 1;
-    rest_pt = (rest_px + 128 * nbr - 1) / (128 * nbr);
-  }
-  if (nbr == 4) { full_pt = pt_all; rest_pt = 0; }
-  const long nwg = (full_pt + rest_pt) * ntn;
+  const long nwg = plan_pp_tiles(a, 128, 512);
   if (nwg <= 0) return GLORIE_OK;
   if (nwg > 0x7fffffffL) return GLORIE_EINVAL;
-  a.pp_full = (int)(full_pt * ntn);
-  a.pp_nbr = nbr;
   const dim3 grid((unsigned)nwg);
+  constexpr size_t lds = 4 * 256 * 128 + 2 * 128 * 128;     // four pixel buffers + two weight stages = 160 KB
   switch (epilogue) {
-    case EPI_BIAS_ACT: launch_ppw_one<EPI_BIAS_ACT>(a, grid, st); break;
-    case EPI_GRU_Q: launch_ppw_one<EPI_GRU_Q>(a, grid, st); break;
-    case EPI_HEADS: launch_ppw_one<EPI_HEADS>(a, grid, st); break;
+    case EPI_BIAS_ACT: launch_kernel<conv_ppw_kernel<EPI_BIAS_ACT>>(a, grid, 512, lds, st); break;
+    case EPI_GRU_Q: launch_kernel<conv_ppw_kernel<EPI_GRU_Q>>(a, grid, 512, lds, st); break;
+    case EPI_HEADS: launch_kernel<conv_ppw_kernel<EPI_HEADS>>(a, grid, 512, lds, st); break;
     default: return GLORIE_EUNSUPPORTED;
   }
   return check_launch();
 }
 
-template <int MB>
+// the haloed 128 x 128 tile (conv_halo_kernel)
 static int launch_conv_halo(const ConvArgs& a, int epilogue, hipStream_t st) {
-  constexpr int PT = 128, TN = 32 * MB;
-  if (a.pair && (MB % 2)) return GLORIE_EINVAL;        // paired weight rows need pairs of 16-row blocks (conv_epilogue_pair)
+  constexpr int PT = 128, TN = 128;
   const long ptiles = (a.P - a.pbeg + PT - 1) / PT;
   if (ptiles <= 0) return GLORIE_OK;
   const long nwg = ptiles * ((a.nout + TN - 1) / TN);
   if (nwg > 0x7fffffffL) return GLORIE_EINVAL;
   const dim3 grid((unsigned)nwg);
-  const size_t lds = halo_lds_bytes(a.W, MB);
+  // weight stage + haloed pixel rows (more than the 16 KB the heads epilogue reduces through)
+  const size_t lds = (size_t)TN * 128 + (size_t)(PT + 2 * (a.W + 1)) * 128;
   switch (epilogue) {
-    case EPI_BIAS_ACT: launch_halo_one<EPI_BIAS_ACT, MB>(a, grid, lds, st); break;
-    case EPI_GRU_ZR: launch_halo_one<EPI_GRU_ZR, MB>(a, grid, lds, st); break;
-    case EPI_GRU_Q:
-      if constexpr (MB == 4) launch_halo_one<EPI_GRU_Q, MB>(a, grid, lds, st);
-      else return GLORIE_EUNSUPPORTED;
-      break;
-    case EPI_HEADS:
-      if constexpr (MB == 4) launch_halo_one<EPI_HEADS, MB>(a, grid, lds, st);
-      else return GLORIE_EUNSUPPORTED;
-      break;
+    case EPI_BIAS_ACT: launch_kernel<conv_halo_kernel<EPI_BIAS_ACT>>(a, grid, 256, lds, st); break;
+    case EPI_GRU_ZR: launch_kernel<conv_halo_kernel<EPI_GRU_ZR>>(a, grid, 256, lds, st); break;
+    case EPI_GRU_Q: launch_kernel<conv_halo_kernel<EPI_GRU_Q>>(a, grid, 256, lds, st); break;
+    case EPI_HEADS: launch_kernel<conv_halo_kernel<EPI_HEADS>>(a, grid, 256, lds, st); break;
     default: return GLORIE_EUNSUPPORTED;
   }
   return check_launch();
 }
 
-template <int NB, int BK, int NW, int ST, int MB = 4>
+// conv_igemm_kernel on tiles of 32 MB channels x 32 NB pixels, at most max_ptiles pixel tiles (< 0: all)
+template <int NB, int MB = 4>
 static int launch_conv(const ConvArgs& a, int epilogue, hipStream_t st, long max_ptiles = -1) {
-  constexpr int PT = (NW / 2) * 16 * NB;
+  constexpr int PT = 32 * NB, TN = 32 * MB;
+  constexpr size_t lds = (size_t)(PT + TN) * 128;      // one stage: pixel tile + weight tile
+  constexpr bool k128 = MB == 4 && NB == 4;            // the epilogues that reduce through LDS exist for this tile only
   if (a.pair && (MB % 2)) return GLORIE_EINVAL;        // paired weight rows need pairs of 16-row blocks (conv_epilogue_pair)
   long ptiles = (a.P - a.pbeg + PT - 1) / PT;
   if (epilogue == EPI_GLO) ptiles = (a.P / a.HW) * ((a.HW + PT - 1) / PT);      // tiles laid per map
   if (max_ptiles >= 0) ptiles = ptiles < max_ptiles ? ptiles : max_ptiles;
   if (ptiles <= 0) return GLORIE_OK;
-  const long nwg = ptiles * ((a.nout + 32 * MB - 1) / (32 * MB));
+  const long nwg = ptiles * ((a.nout + TN - 1) / TN);
   if (nwg > 0x7fffffffL) return GLORIE_EINVAL;
   const dim3 grid((unsigned)nwg);
   switch (epilogue) {
-    case EPI_BIAS_ACT: launch_one<EPI_BIAS_ACT, NB, BK, NW, ST, MB>(a, grid, st); break;
-    case EPI_GRU_ZR: launch_one<EPI_GRU_ZR, NB, BK, NW, ST, MB>(a, grid, st); break;
+    case EPI_BIAS_ACT: launch_kernel<conv_igemm_kernel<EPI_BIAS_ACT, NB, MB>>(a, grid, 256, lds, st); break;
+    case EPI_GRU_ZR: launch_kernel<conv_igemm_kernel<EPI_GRU_ZR, NB, MB>>(a, grid, 256, lds, st); break;
     case EPI_GLO:
-      if constexpr (MB == 4 && NB == 4 && NW == 4 && ST == 1) launch_one<EPI_GLO, NB, BK, NW, ST, MB>(a, grid, st);
+      if constexpr (k128) launch_kernel<conv_igemm_kernel<EPI_GLO, NB, MB>>(a, grid, 256, lds, st);
       else return GLORIE_EUNSUPPORTED;
       break;
     case EPI_HEADS:
-      if constexpr (MB == 4 && NB == 4 && NW == 4 && ST == 1) launch_one<EPI_HEADS, NB, BK, NW, ST, MB>(a, grid, st);
+      if constexpr (k128) launch_kernel<conv_igemm_kernel<EPI_HEADS, NB, MB>>(a, grid, 256, lds, st);
       else return GLORIE_EUNSUPPORTED;
       break;
     case EPI_UPSAMPLE:
-      if constexpr (MB == 4 && NB == 4 && NW == 4 && ST == 1) launch_one<EPI_UPSAMPLE, NB, BK, NW, ST, MB>(a, grid, st);
+      if constexpr (k128) launch_kernel<conv_igemm_kernel<EPI_UPSAMPLE, NB, MB>>(a, grid, 256, lds, st);
       else return GLORIE_EUNSUPPORTED;
       break;
-    default: launch_one<EPI_GRU_Q, NB, BK, NW, ST, MB>(a, grid, st); break;
+    default: launch_kernel<conv_igemm_kernel<EPI_GRU_Q, NB, MB>>(a, grid, 256, lds, st); break;
   }
   return check_launch();
 }
@@ -1746,8 +1511,7 @@ static int conv_igemm_impl(const void* xa, int xa_stride, int ca, const void* xb
   a.tap_w = reinterpret_cast<const f16x8*>(tap_w); a.tap_out = tap_out; a.tap_groups = tap_groups;
   a.tap_ncols = tap_ncols;
   a.up_disps = up_disps; a.up_ix = up_ix; a.up_out = up_out; a.up_f32 = up_f32;
-  // the context term joins in the epilogue (16-byte pieces with paired weights; rounds 2-3 seeded the accumulators with it
-  // through an LDS image of the [pixel][channel] tile, which the paired channel order made obsolete)
+  // the context term joins in the epilogue (16-byte pieces with paired weights)
   a.pair = pair;
   a.pp_full = 0; a.pp_nbr = 4;
 #ifdef EXP_CONV_STAMPS
@@ -1765,7 +1529,7 @@ static int conv_igemm_impl(const void* xa, int xa_stride, int ca, const void* xb
   // Measured on the update operator's layers at 36x60x80 (tools/bench_conv.py): the single-stage
   // 128x128 tile at 3 workgroups per CU (1050 TFLOP/s on the 448->256 layer) beats every variant with
   // more LDS stages and fewer resident workgroups: 2 stages 930, 2 stages + register-resident fragments
-  // (loads two steps ahead, ST = 4) 915, 8 waves with a 3-stage ring and counted vmcnt 830, 256-pixel
+  // (loads two steps ahead) 915, 8 waves with a 3-stage ring and counted vmcnt 830, 256-pixel
   // tiles 850, 32-channel steps at 4 workgroups per CU 824; the same wave tile on v_mfma_f32_32x32x16_f16
   // (16 instead of 32 MFMAs per step) 945.
   // 3x3 layers on the 128-channel tile: the pixel tile is shared by the nine taps of a chunk (conv_halo_kernel) while its haloed
@@ -1788,12 +1552,12 @@ static int conv_igemm_impl(const void* xa, int xa_stride, int ca, const void* xb
       const long tiles128 = (a.P + 127) / 128 * ((nout + 127) / 128);
       if (nout > 64 && (nout & 255) != 0 && W <= 83 && (epilogue <= EPI_GRU_Q || epilogue == EPI_HEADS) &&
           !(epilogue == EPI_BIAS_ACT && tiles128 <= 384))
-        return launch_conv_halo<4>(a, epilogue, st);
+        return launch_conv_halo(a, epilogue, st);
     }
   }
-  if (epilogue == EPI_HEADS || epilogue == EPI_UPSAMPLE) return launch_conv<4, 64, 4, 1>(a, epilogue, st);
+  if (epilogue == EPI_HEADS || epilogue == EPI_UPSAMPLE) return launch_conv<4>(a, epilogue, st);
   // layers with <= 64 output channels (flow_encoder[2]) use a 64-channel tile instead of padding to 128
-  if (nout <= 64 && epilogue == EPI_BIAS_ACT) return launch_conv<4, 64, 4, 1, 2>(a, epilogue, st);
+  if (nout <= 64 && epilogue == EPI_BIAS_ACT) return launch_conv<4, 2>(a, epilogue, st);
   // Tile choice.  Default: 128 x 128 (3 workgroups per CU); layers whose output channels are a multiple of 256 (the z|r
   // gates) take 256 channels x 128 pixels - 4 waves of 128 x 64, 2 workgroups per CU, 25 % fewer staged bytes per MFMA:
   // 448 -> 256 at 36x60x80 345 -> 315 us, the fused gate launch 277 -> 265 us stand-alone.
@@ -1817,22 +1581,22 @@ static int conv_igemm_impl(const void* xa, int xa_stride, int ca, const void* xb
   // 256-pixel tiles: the ping-pong kernel (z|r gate launch at G8 251 -> 234 us in an interleaved A/B, tools/bench_conv.py)
   if (policy == 0 && (nout & 255) == 0 && taps == 9 && epilogue <= EPI_GRU_ZR && a.P >= 256L * 256)
     return launch_conv_pp(a, epilogue, st);
-  if (t0c == 0 && (nout & 255) == 0) return launch_conv<4, 64, 4, 1, 8>(a, epilogue, st);
+  if (t0c == 0 && (nout & 255) == 0) return launch_conv<4, 8>(a, epilogue, st);
   // small launches (GraphAgg's convolutions run on the 8 keyframe maps, 300 pixel tiles): 128-pixel tiles would leave most
   // of the 768 workgroup slots empty and every CU with one latency-bound workgroup - 64-pixel tiles double the workgroups
-  if (t0c == 0 && epilogue == EPI_BIAS_ACT && (a.P + 127) / 128 * ntn <= 384) return launch_conv<2, 64, 4, 1>(a, epilogue, st);
+  if (t0c == 0 && epilogue == EPI_BIAS_ACT && (a.P + 127) / 128 * ntn <= 384) return launch_conv<2>(a, epilogue, st);
   // 1x1 layers have two to four K steps: prologue and epilogue dominate and more, smaller workgroups hide them better
   // (corr_encoder[0] 256 -> 128 at 36x60x80: 33.7 -> 31.8 us)
-  if (t0c == 0 && epilogue == EPI_BIAS_ACT && taps == 1) return launch_conv<2, 64, 4, 1>(a, epilogue, st);
-  if (t0c == 'w') return launch_conv<8, 64, 4, 1, 4>(a, epilogue, st);
-  if (t0c == '6') return launch_conv<2, 64, 4, 1>(a, epilogue, st);
+  if (t0c == 0 && epilogue == EPI_BIAS_ACT && taps == 1) return launch_conv<2>(a, epilogue, st);
+  if (t0c == 'w') return launch_conv<8>(a, epilogue, st);
+  if (t0c == '6') return launch_conv<2>(a, epilogue, st);
   if (t0c == 's' && full_rounds >= 1) {
-    const int rc_a = launch_conv<4, 64, 4, 1>(a, epilogue, st, pt_a);
+    const int rc_a = launch_conv<4>(a, epilogue, st, pt_a);
     if (rc_a != GLORIE_OK) return rc_a;
     a.pbeg = pt_a * 128;
-    return a.pbeg < a.P ? launch_conv<2, 64, 4, 1>(a, epilogue, st) : GLORIE_OK;
+    return a.pbeg < a.P ? launch_conv<2>(a, epilogue, st) : GLORIE_OK;
   }
-  return launch_conv<4, 64, 4, 1>(a, epilogue, st);
+  return launch_conv<4>(a, epilogue, st);
 }
 
 extern "C" int glorie_conv_igemm(const void* xa, int xa_stride, int ca, const void* xb, int xb_stride,

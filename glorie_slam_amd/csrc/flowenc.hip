@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void flow_pad_kernel(const float4* __restrict_
 // pixels of the padded motion map that the tile's stencils touch are staged in LDS once (3.3 KB); a wave owns 32 hidden
 // channels (14 weight fragments, loaded once per workgroup) and walks all 12 pixel blocks.  A hidden pixel OUTSIDE the map is
 // the 3x3 layer's zero padding, not a value of the 7x7 layer: it is written as zeros.
-// Stage 2 is the 3x3 layer of conv_igemm_kernel<EPI_BIAS_ACT, 4, 64, 4, 1, 2> on that tile: a wave owns 32 output channels
+// Stage 2 is the 3x3 layer of conv_igemm_kernel<EPI_BIAS_ACT, 4, 2> on that tile: a wave owns 32 output channels
 // (two 16-row blocks of the paired weight layout) x 4 tile rows of 16 pixels; K runs 64-channel chunk outermost, the nine
 // taps inside, the two 32-wide slices of a chunk in order, so every accumulator sees the MFMA sequence of the two-launch
 // path and the output is bit-identical.  The pixel fragments are ds_read_b128 at the tap's row / column offset in the hidden

@@ -75,7 +75,7 @@ def gate_case():
 def tile_modes():
     """the z|r and q gate launches and the 128 -> 384 head convolution under the three tile policies of glorie_conv_igemm"""
     dev = torch.device("cuda:0")
-    h, w = 60, 80
+    n, h, w = 36, 60, 80
     torch.manual_seed(2)
     cl = lambda c: torch.randn(n, c, h, w, device=dev).half().contiguous(memory_format=torch.channels_last)
     net, wide, pre = cl(128), cl(320), cl(384)
