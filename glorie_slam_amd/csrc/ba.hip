@@ -1346,11 +1346,7 @@ int ba_prepare(const BaWork& wk, const int64_t* ii, int B, int N, int M, int t0,
                hipStream_t st) {
   const size_t prep_lds = sizeof(int) * ((size_t)3 * B + (size_t)N);
   if (prep_lds > 150 * 1024) return GLORIE_EUNSUPPORTED;
-  static PerDeviceOnce attr_set;
-  if (attr_set.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ba_prepare_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-  }
+  GLORIE_TRY(lds_opt_in<ba_prepare_kernel>(150 * 1024));
   hipLaunchKernelGGL(ba_prepare_kernel, dim3(1), dim3(1024), prep_lds, st, wk, ii, B, N, M, t0, t1);
   return check_launch();
 }
@@ -1426,13 +1422,8 @@ static int ba_plan(glorie_ctx* ctx, int B, int N, int M, int h, int w, int t0, i
   wk.dx = reinterpret_cast<float*>(base + o_dx);
   wk.gate = ctx->ba_gate;
   wk.gate_hits = nullptr;
-  static PerDeviceOnce attr_set;
-  if (attr_set.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_fused_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ba_solve_band_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-  }
+  GLORIE_TRY(lds_opt_in<ba_solve_fused_kernel>(160 * 1024 - 64));
+  GLORIE_TRY(lds_opt_in<ba_solve_band_kernel>(160 * 1024 - 64));
   return GLORIE_OK;
 }
 

@@ -1334,17 +1334,11 @@ __global__ __launch_bounds__(512, 1) void conv_ppw_kernel(ConvArgs a) {
 #endif
 }
 
-// Launch of any of the kernels.  More than 64 KB of dynamic LDS needs the opt-in per kernel and device; it is renewed whenever
-// a launch asks for more than was granted so far (conv_halo_kernel's LDS grows with the image width)
+// Launch of any of the kernels (conv_halo_kernel's LDS grows with the image width: launch_lds renews the opt-in)
 template <auto Kernel>
-static void launch_kernel(const ConvArgs& a, dim3 grid, int threads, size_t lds, hipStream_t st) {
-  static size_t granted[kMaxDevices] = {};
-  size_t& g = granted[current_device()];
-  if (lds > 64 * 1024 && lds > g) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    g = lds;
-  }
-  hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, st, a);
+static int launch_kernel(const ConvArgs& a, dim3 grid, int threads, size_t lds, hipStream_t st) {
+  GLORIE_TRY(launch_lds<Kernel>(grid, dim3(threads), lds, st, a));
+  return check_launch();
 }
 
 // Tile plan of the ping-pong kernels, tiles of tn channels x full_px pixels: whole rounds of full tiles (one workgroup per CU,
@@ -1384,11 +1378,10 @@ static int launch_conv_pp(const ConvArgs& a_, int epilogue, hipStream_t st) {
   const dim3 grid((unsigned)nwg);
   constexpr size_t lds = 5 * 256 * 128;                     // two pixel stages + three weight stages
   switch (epilogue) {
-    case EPI_BIAS_ACT: launch_kernel<conv_pp_kernel<EPI_BIAS_ACT>>(a, grid, 512, lds, st); break;
-    case EPI_GRU_ZR: launch_kernel<conv_pp_kernel<EPI_GRU_ZR>>(a, grid, 512, lds, st); break;
+    case EPI_BIAS_ACT: return launch_kernel<conv_pp_kernel<EPI_BIAS_ACT>>(a, grid, 512, lds, st);
+    case EPI_GRU_ZR: return launch_kernel<conv_pp_kernel<EPI_GRU_ZR>>(a, grid, 512, lds, st);
     default: return GLORIE_EUNSUPPORTED;
   }
-  return check_launch();
 }
 
 // 128-channel x 512-pixel ping-pong tiles (conv_ppw_kernel): layers whose output channels are a multiple of 128
@@ -1401,12 +1394,11 @@ static int launch_conv_ppw(const ConvArgs& a_, int epilogue, hipStream_t st) {
   const dim3 grid((unsigned)nwg);
   constexpr size_t lds = 4 * 256 * 128 + 2 * 128 * 128;     // four pixel buffers + two weight stages = 160 KB
   switch (epilogue) {
-    case EPI_BIAS_ACT: launch_kernel<conv_ppw_kernel<EPI_BIAS_ACT>>(a, grid, 512, lds, st); break;
-    case EPI_GRU_Q: launch_kernel<conv_ppw_kernel<EPI_GRU_Q>>(a, grid, 512, lds, st); break;
-    case EPI_HEADS: launch_kernel<conv_ppw_kernel<EPI_HEADS>>(a, grid, 512, lds, st); break;
+    case EPI_BIAS_ACT: return launch_kernel<conv_ppw_kernel<EPI_BIAS_ACT>>(a, grid, 512, lds, st);
+    case EPI_GRU_Q: return launch_kernel<conv_ppw_kernel<EPI_GRU_Q>>(a, grid, 512, lds, st);
+    case EPI_HEADS: return launch_kernel<conv_ppw_kernel<EPI_HEADS>>(a, grid, 512, lds, st);
     default: return GLORIE_EUNSUPPORTED;
   }
-  return check_launch();
 }
 
 // the haloed 128 x 128 tile (conv_halo_kernel)
@@ -1420,13 +1412,12 @@ static int launch_conv_halo(const ConvArgs& a, int epilogue, hipStream_t st) {
   // weight stage + haloed pixel rows (more than the 16 KB the heads epilogue reduces through)
   const size_t lds = (size_t)TN * 128 + (size_t)(PT + 2 * (a.W + 1)) * 128;
   switch (epilogue) {
-    case EPI_BIAS_ACT: launch_kernel<conv_halo_kernel<EPI_BIAS_ACT>>(a, grid, 256, lds, st); break;
-    case EPI_GRU_ZR: launch_kernel<conv_halo_kernel<EPI_GRU_ZR>>(a, grid, 256, lds, st); break;
-    case EPI_GRU_Q: launch_kernel<conv_halo_kernel<EPI_GRU_Q>>(a, grid, 256, lds, st); break;
-    case EPI_HEADS: launch_kernel<conv_halo_kernel<EPI_HEADS>>(a, grid, 256, lds, st); break;
+    case EPI_BIAS_ACT: return launch_kernel<conv_halo_kernel<EPI_BIAS_ACT>>(a, grid, 256, lds, st);
+    case EPI_GRU_ZR: return launch_kernel<conv_halo_kernel<EPI_GRU_ZR>>(a, grid, 256, lds, st);
+    case EPI_GRU_Q: return launch_kernel<conv_halo_kernel<EPI_GRU_Q>>(a, grid, 256, lds, st);
+    case EPI_HEADS: return launch_kernel<conv_halo_kernel<EPI_HEADS>>(a, grid, 256, lds, st);
     default: return GLORIE_EUNSUPPORTED;
   }
-  return check_launch();
 }
 
 // conv_igemm_kernel on tiles of 32 MB channels x 32 NB pixels, at most max_ptiles pixel tiles (< 0: all)
@@ -1444,23 +1435,19 @@ static int launch_conv(const ConvArgs& a, int epilogue, hipStream_t st, long max
   if (nwg > 0x7fffffffL) return GLORIE_EINVAL;
   const dim3 grid((unsigned)nwg);
   switch (epilogue) {
-    case EPI_BIAS_ACT: launch_kernel<conv_igemm_kernel<EPI_BIAS_ACT, NB, MB>>(a, grid, 256, lds, st); break;
-    case EPI_GRU_ZR: launch_kernel<conv_igemm_kernel<EPI_GRU_ZR, NB, MB>>(a, grid, 256, lds, st); break;
+    case EPI_BIAS_ACT: return launch_kernel<conv_igemm_kernel<EPI_BIAS_ACT, NB, MB>>(a, grid, 256, lds, st);
+    case EPI_GRU_ZR: return launch_kernel<conv_igemm_kernel<EPI_GRU_ZR, NB, MB>>(a, grid, 256, lds, st);
     case EPI_GLO:
-      if constexpr (k128) launch_kernel<conv_igemm_kernel<EPI_GLO, NB, MB>>(a, grid, 256, lds, st);
+      if constexpr (k128) return launch_kernel<conv_igemm_kernel<EPI_GLO, NB, MB>>(a, grid, 256, lds, st);
       else return GLORIE_EUNSUPPORTED;
-      break;
     case EPI_HEADS:
-      if constexpr (k128) launch_kernel<conv_igemm_kernel<EPI_HEADS, NB, MB>>(a, grid, 256, lds, st);
+      if constexpr (k128) return launch_kernel<conv_igemm_kernel<EPI_HEADS, NB, MB>>(a, grid, 256, lds, st);
       else return GLORIE_EUNSUPPORTED;
-      break;
     case EPI_UPSAMPLE:
-      if constexpr (k128) launch_kernel<conv_igemm_kernel<EPI_UPSAMPLE, NB, MB>>(a, grid, 256, lds, st);
+      if constexpr (k128) return launch_kernel<conv_igemm_kernel<EPI_UPSAMPLE, NB, MB>>(a, grid, 256, lds, st);
       else return GLORIE_EUNSUPPORTED;
-      break;
-    default: launch_kernel<conv_igemm_kernel<EPI_GRU_Q, NB, MB>>(a, grid, 256, lds, st); break;
+    default: return launch_kernel<conv_igemm_kernel<EPI_GRU_Q, NB, MB>>(a, grid, 256, lds, st);
   }
-  return check_launch();
 }
 
 }  // namespace glorie

@@ -55,8 +55,7 @@ using namespace glorie;
 
 extern "C" int glorie_corr_build(const void* fmaps_cl, const int64_t* ii, const int64_t* jj, const int* slots,
                                  void* const* levels, int num_levels, int n_new, int h, int w, int C, void* stream) {
-  static PerDeviceOnce attr;
   // widths that are not multiples of 8 keep the torch builder
-  return corr_build_launch<TiledPad>(corr_build_kernel, attr, fmaps_cl, ii, jj, slots, levels, num_levels, n_new, h, w, C,
+  return corr_build_launch<corr_build_kernel, TiledPad>(fmaps_cl, ii, jj, slots, levels, num_levels, n_new, h, w, C,
                                      stream, [&] { return (w & 7) ? 0 : (h * w + 31) / 32; });
 }

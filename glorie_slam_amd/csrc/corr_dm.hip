@@ -628,8 +628,7 @@ extern "C" long glorie_corr_dm_level_halfs(int h, int w, int level) {
 
 extern "C" int glorie_corr_dm_build(const void* fmaps_cl, const int64_t* ii, const int64_t* jj, const int* slots,
                                     void* const* levels, int num_levels, int n_new, int h, int w, int C, void* stream) {
-  static PerDeviceOnce attr;
-  return corr_build_launch<DmPad>(corr_dm_build_kernel, attr, fmaps_cl, ii, jj, slots, levels, num_levels, n_new, h, w, C,
+  return corr_build_launch<corr_dm_build_kernel, DmPad>(fmaps_cl, ii, jj, slots, levels, num_levels, n_new, h, w, C,
                                   stream, [&] {     // a workgroup = half a source tile; the last level must not be empty
                                     const bool ok = (h >> (num_levels - 1)) >= 1 && (w >> (num_levels - 1)) >= 1;
                                     return ok ? ((w + 7) / 8) * ((h + 7) / 8) * 2 : 0;
@@ -667,13 +666,6 @@ extern "C" int glorie_corr_dm_lookup(const void* const* levels, const int* slots
     return check_launch();
   }
   const size_t lds = sizeof(_Float16) * 128 * kEnc2Lds + 256 * sizeof(float) + 4 * 4096;   // weights, bias, store stages
-  static PerDeviceOnce enc_attr;
-  if (enc_attr.first()) {
-    GLORIE_TRY(check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_dm_encode_kernel<false>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)));
-    GLORIE_TRY(check_hip(hipFuncSetAttribute(reinterpret_cast<const void*>(corr_dm_encode_kernel<true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)));
-  }
   // the output rows are stored through a buffer descriptor (32-bit offsets, out-of-map lanes dropped by its range check):
   // a call whose rows span 2 GB or more is issued in runs of edges
   const size_t edge_bytes = (size_t)h * w * enc_stride * sizeof(_Float16);
@@ -690,8 +682,8 @@ extern "C" int glorie_corr_dm_lookup(const void* const* levels, const int* slots
     c.enc_out = a.enc_out + (size_t)n0 * h * w * enc_stride;
     c.enc_bytes = (unsigned)(edge_bytes * c.N);
     const unsigned blocks = (unsigned)(((long)c.N * a.ntx * a.nty + 3) / 4);
-    if (corr_cl) hipLaunchKernelGGL((corr_dm_encode_kernel<true>), dim3(blocks), dim3(256), lds, st, c);
-    else hipLaunchKernelGGL((corr_dm_encode_kernel<false>), dim3(blocks), dim3(256), lds, st, c);
+    if (corr_cl) GLORIE_TRY(launch_lds<corr_dm_encode_kernel<true>>(dim3(blocks), dim3(256), lds, st, c));
+    else GLORIE_TRY(launch_lds<corr_dm_encode_kernel<false>>(dim3(blocks), dim3(256), lds, st, c));
   }
   return check_launch();
 }

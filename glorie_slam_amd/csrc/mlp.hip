@@ -1,7 +1,7 @@
 // Fused neural-point decoders on the matrix cores (scope row R3) for gfx950.
 //
 // Replaces the chains of small nn.Linear launches of
-//   MLP_geometry.forward   /root/reference/src/modules/conv_onet/models/decoder.py:175-225
+//   MLP_geometry.forward   (reference) src/modules/conv_onet/models/decoder.py:175-225
 //   MLP_color.get_feature_at_pos (per-neighbour F_theta)              decoder.py:340-389, 228-243
 //   MLP_color.forward                                                 decoder.py:391-433
 // with three kernels that keep every activation in registers:
@@ -12,12 +12,13 @@
 //   col  : [sin,cos](p B)(40) ++ [sin,cos](v B)(40) -> 5 x (Linear(128) softplus + fc_c(c)),
 //          skip at layer 2 -> sigmoid rgb
 //
-// All GEMMs are exact fp32 on v_mfma_f32_16x16x4_f32 (the reference runs fp32; no xf32 on gfx950), in the
-// transposed form  H'^T = W^T H^T : the 16 MFMA rows are output channels (A = weights from LDS), the 16
+// Each kernel exists twice around a different MFMA core: exact fp32 on v_mfma_f32_16x16x4_f32 (mlp_*_v3; the reference
+// runs fp32, no xf32 on gfx950) and the 3-term fp16 split on v_mfma_f32_16x16x32_f16 (mlp_geo_v4 / mlp_nb_v4 / mlp_col_v5,
+// the product path).  Everything around the core - gathers, embeddings, activations, output layers, staging - is shared.
+// All GEMMs run in the transposed form  H'^T = W^T H^T : the 16 MFMA rows are output channels (A = weights from LDS), the 16
 // columns are a wave's 16 samples (B = activations).  The accumulator fragment of one layer is then
-// directly the B fragment of the next (see mlp_col_v3_kernel), so no activation ever touches LDS.  A
-// workgroup = 8 waves = 128 samples; the skip connection is two GEMMs on the split weight (embedding
-// rows / hidden rows) - the concatenated activation is never built.
+// directly the B fragment of the next (see mlp_col_v3_kernel), so no activation ever touches LDS.  The skip connection is
+// two GEMMs on the split weight (embedding rows / hidden rows) - the concatenated activation is never built.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -27,24 +28,19 @@
 namespace glorie {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;
 
 template <int NT>
 __device__ __forceinline__ void zero(f32x4 (&acc)[NT]) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
+__device__ __forceinline__ f32x4 as_f32x4(const float4 v) { return f32x4{v.x, v.y, v.z, v.w}; }
 
-// ---- packed parameters (device pointers into one buffer, see point_ops.pack_decoders) ----
+// ---- packed parameters (device pointers into one buffer, see kPackFloats below and point_ops.pack_decoders) ----
+// Only what a kernel reads through a pointer is here; the layer weights travel as the LDS images / fragments.
 struct GeoParams {
   const float* B;          // [3][96]   Fourier matrix (93 cols, zero padded)
-  const float* W0;         // [96][32]
-  const float* W1;         // [32][32]
-  const float* W2;         // [32][32]
-  const float* W3e;        // [96][32]  embedding rows of the skip layer
-  const float* W3h;        // [32][32]  hidden rows of the skip layer
-  const float* W4;         // [32][32]
-  const float* Wout;       // [32][16]  (col 0 real)
-  const float* Fc;         // [5][32][32]
   const float* bias;       // [5][32]   pts_linears biases
   const float* fcb;        // [5][32]   fc_c biases
   const float* bout;       // [4]       output bias (element 0)
@@ -61,24 +57,30 @@ struct NbParams {
 struct ColParams {
   const float* Bp;         // [3][20]
   const float* Bv;         // [3][20]
-  const float* W0;         // [80][128]
-  const float* W1;         // [128][128]
-  const float* W2;         // [128][128]
-  const float* W3e;        // [80][128]
-  const float* W3h;        // [128][128]
-  const float* W4;         // [128][128]
   const float* Wout;       // [128][16] (cols 0..2 real)
-  const float* Fc;         // [5][32][128]
   const float* bias;       // [5][128]
   const float* fcb;        // [5][128]
   const float* bout;       // [4]       output bias (rgb)
 };
 
 // ====================================================================================
-// 128 samples / 8 waves per workgroup.  The colour weights (442 KB) are streamed through LDS in 32-row
-// chunks (double buffered, shared by the 8 waves); the geometry and per-neighbour weights are resident.
+// 128 samples per workgroup.  The colour weights (442 KB) are streamed through LDS in 32-row
+// chunks (double buffered, shared by the waves); the geometry and per-neighbour weights are resident.
 // ====================================================================================
 constexpr int kTM2 = 128;
+
+// Lane (r, g) of wave wv: MFMA column r = a sample, k-slot / accumulator row group g.  qs is the lane's sample when the
+// wave's 16-sample column blocks are numbered wv * nb + b from sample q0 on (all four k-slots of a column share it),
+// q the same clamped into [0, Q) for the loads of a ragged last workgroup
+struct Lane { int wv, lane, r, g, qs, q; };
+__device__ __forceinline__ Lane lane_of(int q0, int Q, int nb = 1, int b = 0) {
+  Lane L;
+  L.wv = threadIdx.x >> 6; L.lane = threadIdx.x & 63;
+  L.r = L.lane & 15; L.g = L.lane >> 4;
+  L.qs = q0 + (L.wv * nb + b) * 16 + L.r;
+  L.q = min(L.qs, Q - 1);
+  return L;
+}
 
 // torch.nn.Softplus(beta=100, threshold=20) on the bare base-2 hardware transcendentals (v_exp_f32 /
 // v_log_f32, 1 ulp each), in the overflow-free form
@@ -97,24 +99,156 @@ __device__ __forceinline__ float softplus100_fast(float x) {
 __device__ __forceinline__ float sin_rev(float rev) { return __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(rev)); }
 __device__ __forceinline__ float cos_rev(float rev) { return __builtin_amdgcn_cosf(__builtin_amdgcn_fractf(rev)); }
 
-struct ChunkRegs { float4 a, b; };
-
-// thread t of 512 moves 8 floats: row = t >> 4 (0..31), cols (t & 15) * 8 .. + 7
-__device__ __forceinline__ ChunkRegs chunk_load(const float* __restrict__ Wall, int chunk) {
-  const int t = threadIdx.x;
-  const float4* src = reinterpret_cast<const float4*>(Wall + ((size_t)chunk * 32 + (t >> 4)) * 128 + (t & 15) * 8);
-  ChunkRegs r;
-  r.a = src[0];
-  r.b = src[1];
-  return r;
+// ---- 3-term fp16 split ----------------------------------------------------------------------------------------------
+// The fp32 MFMA (16x16x4, 64 flops per cycle and SIMD) is the slowest matrix path of the chip; the fp16 one (16x16x32) is
+// 16x faster.  Every weight and activation is split as x = hi + lo (hi = fp16(x), lo = fp16(x - hi): 22 mantissa bits) and
+// a product is accumulated as hi*hi + hi*lo + lo*hi in fp32 - the dropped lo*lo term is 2^-22 relative, the fp16 products
+// are exact in the fp32 accumulator - so a 32-row chunk costs 3 x 8 MFMAs of 16 cycles instead of 64 of 32.  The
+// transposed formulation carries over: the accumulator blocks (2t, 2t+1) of a layer, split and packed, are the eight
+// k-slots of a lane's B operand for chunk t of the next layer (slot s <-> chunk row 16 (s >> 2) + 4 g + (s & 3), the same
+// row order as the fp32 chunks); the weights are packed once per chunk as A fragments
+// [hi|lo][out block][lane 64][8 halfs] (point_ops.pack_decoders) and copied to LDS as they are (linear copy,
+// conflict-free ds_read_b128).  Activations, biases and the output layers stay fp32 as in the exact kernels.
+//
+// split two accumulator blocks (channels 4g + rr of block 0 -> slots 0..3, of block 1 -> slots 4..7) into hi / lo halfs
+__device__ __forceinline__ void split2(const f32x4 a, const f32x4 b, h16x8& hi, h16x8& lo) {
+  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    hi[s] = (_Float16)v[s];
+#ifdef EXP_MLP_NO_SPLIT
+    lo[s] = (_Float16)0.0f;                                 // ablation: the cost of forming the low halves
+#else
+    lo[s] = (_Float16)(v[s] - (float)hi[s]);
+#endif
+  }
 }
-// ---- geometry decoder, transposed formulation (see the colour decoder below for the idea) ----------------
-// All weights of the network (480 K-rows of 32 outputs, 61 KB, + the 32 x 16 output layer) are staged once per
-// workgroup as the LDS image built by point_ops.pack_decoders: row k holds output 16 to + r at 2 r + to, so
+// acc += A B for one A fragment pair of a split chunk (the three kept terms, in this order everywhere)
+__device__ __forceinline__ f32x4 mfma_h3(const h16x8 ahi, const h16x8 alo, const h16x8 bhi, const h16x8 blo, f32x4 acc) {
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc, 0, 0, 0);
+}
+// Range guard of the split kernels.  The split holds |x| <= 65504 (fp16 max).  A larger operand becomes hi = inf,
+// lo = x - inf = -inf, and its products a.hi * inf + a.hi * (-inf) are NaN in EVERY output channel it feeds; softplus, the
+// (NaN-keeping) ReLU below, the biases, the next split and the fp32 output layers all pass a NaN on, so an overflow anywhere
+// in a network surfaces as a non-finite value at its output.  The kernels therefore test only what they are about to store
+// (a handful of values per lane - tracking max |x| at every split costs ~100 registers' worth of spills in the colour
+// kernel) and raise the caller's flag; the host then repeats the call on the exact-fp32 MFMA kernels.  (Small magnitudes are
+// safe: below 2^-3 the low half falls into fp16 subnormals and the split's error becomes ABSOLUTE, 2^-25 per operand.)
+// The shared output helpers return the test's result; the exact kernels drop it.
+__device__ __forceinline__ bool not_finite(float x) { return !(__builtin_fabsf(x) <= 3.0e38f); }
+__device__ __forceinline__ void report_range(bool bad, int* __restrict__ range_flag) {
+  if (range_flag && __builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(range_flag, 1);
+}
+
+// ---- hidden-layer activation: acc = F(acc + bias) + fc_c bias, NT 16-channel blocks of NB column blocks ----------------
+__device__ __forceinline__ float relu(float x) { return fmaxf(x, 0.0f); }
+__device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.0f ? 0.0f : x; }
+
+template <float (*F)(float), int NT, int NB>
+__device__ __forceinline__ void act_layer(f32x4 (*acc)[NT], const float* bias, const float* fcb, int li, int g) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const float4 bb = *reinterpret_cast<const float4*>(bias + li * (16 * NT) + 16 * t + 4 * g);
+    const float4 fb = *reinterpret_cast<const float4*>(fcb + li * (16 * NT) + 16 * t + 4 * g);
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      acc[nb][t][0] = F(acc[nb][t][0] + bb.x) + fb.x;
+      acc[nb][t][1] = F(acc[nb][t][1] + bb.y) + fb.y;
+      acc[nb][t][2] = F(acc[nb][t][2] + bb.z) + fb.z;
+      acc[nb][t][3] = F(acc[nb][t][3] + bb.w) + fb.w;
+    }
+  }
+}
+
+// ====================================================================================
+// geometry decoder
+// ====================================================================================
+// Exact kernel: all weights of the network (480 K-rows of 32 outputs, 61 KB, + the 32 x 16 output layer) are staged once
+// per workgroup as the LDS image built by point_ops.pack_decoders: row k holds output 16 to + r at 2 r + to, so
 // one ds_read_b64 per lane fetches the A operands of the two 16-channel output blocks.  Embedding (96, sin),
 // feature c (32) and hidden state (32) live in registers as B fragments; no barrier after the staging.
+// Split kernel: the 480 K-rows are 15 chunks of 32, packed as A fragments [chunk][hi|lo][out block 2][lane 64][8 halfs]
+// (1024 floats per chunk), staged once per workgroup and followed by the same fp32 output layer.
 constexpr int kGeoRows = 480;
-constexpr int kGeoImage = kGeoRows * 32 + 32 * 16;   // floats
+constexpr int kGeoOut = 32 * 16;                     // the 32 -> 1 output layer, 16 padded columns, natural order
+constexpr int kGeoImage = kGeoRows * 32 + kGeoOut;   // floats
+constexpr int kGeoFrag = 15 * 1024;                  // floats
+
+// one 16-feature block t of the embedding as a B fragment: sin of the phases of channels 16t + 4g + rr.  Columns 93..95 of
+// B are zero padding (sin 0 = 0) and so are the matching weight rows
+__device__ __forceinline__ f32x4 geo_embed_block(float x, float y, float z, const float* __restrict__ B, int t, int g) {
+  const float4 b0 = *reinterpret_cast<const float4*>(B + 16 * t + 4 * g);
+  const float4 b1 = *reinterpret_cast<const float4*>(B + 96 + 16 * t + 4 * g);
+  const float4 b2 = *reinterpret_cast<const float4*>(B + 192 + 16 * t + 4 * g);
+  f32x4 e;
+  e[0] = sin_rev(fmaf(z, b2.x, fmaf(y, b1.x, x * b0.x)));
+  e[1] = sin_rev(fmaf(z, b2.y, fmaf(y, b1.y, x * b0.y)));
+  e[2] = sin_rev(fmaf(z, b2.z, fmaf(y, b1.z, x * b0.z)));
+  e[3] = sin_rev(fmaf(z, b2.w, fmaf(y, b1.w, x * b0.w)));
+  return e;
+}
+
+#ifndef GLORIE_GEO_NB
+#define GLORIE_GEO_NB 2
+#endif
+// The geometry feature c of sample q as two B fragments (channels 16t + 4g + rr): read from c_geo, or - geo_feats given -
+// the IDW interpolation of the neighbours' features right here (decoder.py:130-173; same summation order as
+// idw_gather_kernel), so that the loads travel with the weights and c_geo never exists in HBM.  NBR_ID(k) / NBR_W(k) yield
+// neighbour k's row (clamped to >= 0) and weight - loaded at this point or long before, the kernel's choice; PREFETCH is
+// placed behind the first gathers, where the split kernel requests its next block's ids.
+// The rows of GEO_NB neighbours are requested together and unconditionally (zero-weight rows dropped by a select - the same
+// bits): a load under `if (wk != 0)` is one exposed L2 round trip per neighbour at the head of every workgroup.
+// A macro, because mlp_geo_v3_kernel lives at 124 of the 128 registers that four waves per SIMD have: with this text in a
+// forced-inline function (ids and weights by pointer or by lambda alike) the compiler orders the same operations into 30
+// spilled registers, and pinning the embedding in front of the call instead (106 registers, no spill) takes its loads out of
+// the gather's shadow: 0.241 against 0.200 ms per 614,400 samples.
+#define GLORIE_IDW_FEATURE(c, c_geo, geo_feats, q, g, on, NBR_ID, NBR_W, PREFETCH)                                      \
+  if (geo_feats) {                                                                                                      \
+    zero<2>(c);                                                                                                         \
+    constexpr int GEO_NB = GLORIE_GEO_NB;                                                                               \
+    _Pragma("unroll") for (int k0 = 0; k0 < 8; k0 += GEO_NB) {                                                          \
+      float wk[GEO_NB];                                                                                                 \
+      float4 v[GEO_NB][2];                                                                                              \
+      _Pragma("unroll") for (int k = 0; k < GEO_NB; ++k) {                                                              \
+        wk[k] = NBR_W(k0 + k);                                                                                          \
+        const auto ik = NBR_ID(k0 + k);                                                                                 \
+        _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                   \
+          v[k][t] = *reinterpret_cast<const float4*>(geo_feats + (size_t)ik * 32 + 16 * t + 4 * g);                     \
+      }                                                                                                                 \
+      if (k0 == 0) { PREFETCH; }                                                                                        \
+      _Pragma("unroll") for (int k = 0; k < GEO_NB; ++k) {                                                              \
+        const bool use = on && wk[k] != 0.0f;                                                                           \
+        _Pragma("unroll") for (int t = 0; t < 2; ++t) {                                                                 \
+          c[t][0] = use ? c[t][0] + wk[k] * v[k][t].x : c[t][0];                                                        \
+          c[t][1] = use ? c[t][1] + wk[k] * v[k][t].y : c[t][1];                                                        \
+          c[t][2] = use ? c[t][2] + wk[k] * v[k][t].z : c[t][2];                                                        \
+          c[t][3] = use ? c[t][3] + wk[k] * v[k][t].w : c[t][3];                                                        \
+        }                                                                                                               \
+      }                                                                                                                 \
+    }                                                                                                                   \
+  } else {                                                                                                              \
+    PREFETCH;                                                                                                           \
+    _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                       \
+      c[t] = as_f32x4(*reinterpret_cast<const float4*>(c_geo + (size_t)q * 32 + 16 * t + 4 * g));                       \
+  }
+
+// output layer 32 -> 1 in fp32 (Wout: [32][16] in LDS): lanes with g == 0 get channel 0 of their sample in o[0] and store
+// the occupancy, -100 where the sample has no neighbour (Renderer.py:206-207).  Returns the range test of what was stored
+__device__ __forceinline__ bool geo_output(const f32x4 (&acc)[2], const float* Wout, const float* __restrict__ bout,
+                                           const Lane& L, int Q, bool on, float* __restrict__ raw) {
+  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float* wp = Wout + (4 * L.g) * 16 + L.r;
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+      o = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 16], acc[t][rr], o, 0, 0, 0);
+  if (L.g != 0 || L.qs >= Q) return false;
+  raw[(size_t)L.qs * 4 + 3] = on ? o[0] + bout[0] : -100.0f;
+  return on && not_finite(o[0]);
+}
 
 template <int NT, int NB>
 __device__ __forceinline__ void mma_geo(f32x4 (&acc)[2], const f32x4 (&b)[NB], const float* Wrows) {
@@ -139,84 +273,24 @@ __global__ __launch_bounds__(512, 4) void mlp_geo_v3_kernel(GeoParams P, const f
                                                             const uint8_t* __restrict__ has, int Q,
                                                             float* __restrict__ raw) {
   extern __shared__ float smem[];
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const int r = lane & 15, g = lane >> 4;
-  const int qs = blockIdx.x * kTM2 + wv * 16 + r;
-  const int q = min(qs, Q - 1);
-  for (int idx = tid; idx < kGeoImage / 4; idx += 512)
+  const Lane L = lane_of(blockIdx.x * kTM2, Q);
+  const int g = L.g;
+  const size_t q = L.q;
+  for (int idx = threadIdx.x; idx < kGeoImage / 4; idx += 512)
     reinterpret_cast<float4*>(smem)[idx] = reinterpret_cast<const float4*>(image)[idx];
   // B fragments: channel 16t + 4g + rr of sample r
   f32x4 e[6], c[2], h[2], acc[2];
-  {
-    const float x = pts[(size_t)q * 3 + 0], y = pts[(size_t)q * 3 + 1], z = pts[(size_t)q * 3 + 2];
+  const float x = pts[q * 3 + 0], y = pts[q * 3 + 1], z = pts[q * 3 + 2];
 #pragma unroll
-    for (int t = 0; t < 6; ++t) {
-      const float4 b0 = *reinterpret_cast<const float4*>(P.B + 16 * t + 4 * g);
-      const float4 b1 = *reinterpret_cast<const float4*>(P.B + 96 + 16 * t + 4 * g);
-      const float4 b2 = *reinterpret_cast<const float4*>(P.B + 192 + 16 * t + 4 * g);
-      e[t][0] = sin_rev(fmaf(z, b2.x, fmaf(y, b1.x, x * b0.x)));
-      e[t][1] = sin_rev(fmaf(z, b2.y, fmaf(y, b1.y, x * b0.y)));
-      e[t][2] = sin_rev(fmaf(z, b2.z, fmaf(y, b1.z, x * b0.z)));
-      e[t][3] = sin_rev(fmaf(z, b2.w, fmaf(y, b1.w, x * b0.w)));
-    }
-    // columns 93..95 of B are zero padding (sin 0 = 0) and so are the matching weight rows
-    if (geo_feats) {
-      // IDW interpolation of the neighbours' features right here (decoder.py:130-173; same summation order
-      // as idw_gather_kernel): the loads travel with the weight image, c_geo never exists in HBM
-      c[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-      c[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const bool on = has[q] != 0;
-      // the rows of GEO_NB neighbours are requested together and unconditionally (index clamped, zero-weight rows dropped
-      // by a select - the same bits): a load under `if (wk != 0)` is one exposed L2 round trip per neighbour at the head
-      // of every workgroup
-#ifndef GLORIE_GEO_NB
-#define GLORIE_GEO_NB 2
-#endif
-      constexpr int GEO_NB = GLORIE_GEO_NB;
-#pragma unroll
-      for (int k0 = 0; k0 < 8; k0 += GEO_NB) {
-        float wk[GEO_NB];
-        float4 v[GEO_NB][2];
-#pragma unroll
-        for (int k = 0; k < GEO_NB; ++k) {
-          wk[k] = wts[(size_t)q * 8 + k0 + k];
-          const long ik = max(I[(size_t)q * 8 + k0 + k], 0L);
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            v[k][t] = *reinterpret_cast<const float4*>(geo_feats + (size_t)ik * 32 + 16 * t + 4 * g);
-        }
-#pragma unroll
-        for (int k = 0; k < GEO_NB; ++k) {
-          const bool use = on && wk[k] != 0.0f;
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            c[t][0] = use ? c[t][0] + wk[k] * v[k][t].x : c[t][0];
-            c[t][1] = use ? c[t][1] + wk[k] * v[k][t].y : c[t][1];
-            c[t][2] = use ? c[t][2] + wk[k] * v[k][t].z : c[t][2];
-            c[t][3] = use ? c[t][3] + wk[k] * v[k][t].w : c[t][3];
-          }
-        }
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float4 v = *reinterpret_cast<const float4*>(c_geo + (size_t)q * 32 + 16 * t + 4 * g);
-        c[t][0] = v.x; c[t][1] = v.y; c[t][2] = v.z; c[t][3] = v.w;
-      }
-    }
-  }
+  for (int t = 0; t < 6; ++t) e[t] = geo_embed_block(x, y, z, P.B, t, g);
+  const bool on = has[q] != 0;
+#define V3_NBR_ID(k) max(I[q * 8 + (k)], 0L)
+#define V3_NBR_W(k) wts[q * 8 + (k)]
+  GLORIE_IDW_FEATURE(c, c_geo, geo_feats, q, g, on, V3_NBR_ID, V3_NBR_W, )
+#undef V3_NBR_W
+#undef V3_NBR_ID
   __syncthreads();
-  auto act = [&](int li) {   // ReLU(acc + bias) + fc_c bias
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float4 bb = *reinterpret_cast<const float4*>(P.bias + li * 32 + 16 * t + 4 * g);
-      const float4 fb = *reinterpret_cast<const float4*>(P.fcb + li * 32 + 16 * t + 4 * g);
-      acc[t][0] = fmaxf(acc[t][0] + bb.x, 0.0f) + fb.x;
-      acc[t][1] = fmaxf(acc[t][1] + bb.y, 0.0f) + fb.y;
-      acc[t][2] = fmaxf(acc[t][2] + bb.z, 0.0f) + fb.z;
-      acc[t][3] = fmaxf(acc[t][3] + bb.w, 0.0f) + fb.w;
-    }
-  };
+  auto act = [&](int li) { act_layer<relu, 2, 1>(&acc, P.bias, P.fcb, li, g); };
   auto next_layer = [&]() {
 #pragma unroll
     for (int t = 0; t < 2; ++t) { h[t] = acc[t]; acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -234,20 +308,119 @@ __global__ __launch_bounds__(512, 4) void mlp_geo_v3_kernel(GeoParams P, const f
   mma_geo<2, 2>(acc, h, W + 352 * 32);    act(3); mma_geo<2, 2>(acc, c, W + 384 * 32);
   next_layer();
   mma_geo<2, 2>(acc, h, W + 416 * 32);    act(4); mma_geo<2, 2>(acc, c, W + 448 * 32);
-  // output layer 32 -> 1 (16 padded columns): lanes with g == 0 get channel 0 of their sample in o[0]
-  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-  {
-    const float* wp = W + kGeoRows * 32 + (4 * g) * 16 + r;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-        o = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 16], acc[t][rr], o, 0, 0, 0);
-  }
-  if (g == 0 && qs < Q) raw[(size_t)qs * 4 + 3] = has[qs] ? o[0] + P.bout[0] : -100.0f;  // Renderer.py:206-207
+  geo_output(acc, W + kGeoRows * 32, P.bout, L, Q, on, raw);
 }
 
-// ---- colour decoder, transposed formulation ------------------------------------------------
+__device__ __forceinline__ void mma_g3(f32x4 (&acc)[2], const h16x8 bhi, const h16x8 blo, const float* chunk) {
+  const h16x8* wp = reinterpret_cast<const h16x8*>(chunk) + (threadIdx.x & 63);
+#pragma unroll
+  for (int to = 0; to < 2; ++to) acc[to] = mfma_h3(wp[to * 64], wp[(2 + to) * 64], bhi, blo, acc[to]);
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// The 96-channel embedding is evaluated where it is consumed (layer 0 and again at the skip layer) instead of being kept:
+// 24 v_sin per sample against 24 registers that the 128-register budget of four waves per SIMD does not have.
+// GO (gather only): the measurement instantiation behind stage_flags bit 2 of glorie_render_mlp - the kernel's R2 phase
+// alone (ids, weights, the 8 feature rows and their interpolation) with the decoder removed, so that bench.py can time the
+// feature pull AS THE PRODUCT PERFORMS IT (inside this kernel, not in a stand-alone gather launch) in its own process.
+template <bool GO>
+__global__ __launch_bounds__(512, 4) void mlp_geo_v4_kernel(GeoParams P, const float* __restrict__ frags,
+                                                            const float* __restrict__ wout,
+                                                            const float* __restrict__ pts,
+                                                            const float* __restrict__ c_geo,
+                                                            const float* __restrict__ geo_feats,
+                                                            const int64_t* __restrict__ I,
+                                                            const float* __restrict__ wts,
+                                                            const uint8_t* __restrict__ has, int Q,
+                                                            float* __restrict__ raw, int* __restrict__ range_flag) {
+  bool bad = false;
+  extern __shared__ float smem[];              // [15][1024] fragments | [32][16] output layer
+  const int tid = threadIdx.x;
+  if constexpr (!GO) {                        // (the weights are no part of the feature pull)
+#pragma unroll 2
+    for (int idx = tid; idx < kGeoFrag / 4; idx += 512)
+      reinterpret_cast<float4*>(smem)[idx] = reinterpret_cast<const float4*>(frags)[idx];
+    if (tid < kGeoOut / 4) reinterpret_cast<float4*>(smem + kGeoFrag)[tid] = reinterpret_cast<const float4*>(wout)[tid];
+  }
+  __syncthreads();
+  // persistent over the sample blocks: the 61 KB of fragments are staged once per workgroup (a launch used to stage them
+  // for every 128 samples, 4800 times per 614k-sample batch, with the first MFMA of a workgroup waiting behind it)
+  const int nblk = (Q + kTM2 - 1) / kTM2;
+  // per-sample inputs of a block: position, neighbour ids, IDW weights.  They are requested one block AHEAD, so a block's
+  // feature gather (which needs the ids) starts at once instead of behind a second dependent memory round trip
+  struct Meta { float x, y, z; int id[8]; float wk[8]; bool on; };
+  auto load_meta = [&](int blk, Meta& m) {
+    const size_t qq = lane_of(blk * kTM2, Q).q;
+    m.x = pts[qq * 3 + 0]; m.y = pts[qq * 3 + 1]; m.z = pts[qq * 3 + 2];
+    m.on = has[qq] != 0;
+    if (geo_feats) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        m.id[k] = (int)max(I[qq * 8 + k], 0L);
+        m.wk[k] = wts[qq * 8 + k];
+      }
+    }
+  };
+  Meta cur;
+  if ((int)blockIdx.x < nblk) load_meta(blockIdx.x, cur);
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const Lane L = lane_of(blk * kTM2, Q);
+    const int g = L.g;
+    h16x8 chi, clo, hhi, hlo;
+    f32x4 acc[2];
+    const float x = cur.x, y = cur.y, z = cur.z;
+    const bool on = cur.on;
+    Meta nxt = cur;
+    {
+      f32x4 c[2];
+#define V4_NBR_ID(k) cur.id[k]
+#define V4_NBR_W(k) cur.wk[k]
+      GLORIE_IDW_FEATURE(c, c_geo, geo_feats, L.q, g, on, V4_NBR_ID, V4_NBR_W,
+                         if (blk + (int)gridDim.x < nblk) load_meta(blk + gridDim.x, nxt))
+#undef V4_NBR_W
+#undef V4_NBR_ID
+      split2(c[0], c[1], chi, clo);
+      if constexpr (GO) {
+        // the interpolated feature's sum stands in for the occupancy
+        if (g == 0 && L.qs < Q) raw[(size_t)L.qs * 4 + 3] = (c[0][0] + c[0][1]) + (c[1][2] + c[1][3]);
+        cur = nxt;
+        continue;
+      }
+    }
+    auto act = [&](int li) { act_layer<relu_keep_nan, 2, 1>(&acc, P.bias, P.fcb, li, g); };
+    auto next_layer = [&]() {
+      split2(acc[0], acc[1], hhi, hlo);
+      zero<2>(acc);
+    };
+    auto ch = [&](int c) { return smem + c * 1024; };
+    // embedding blocks (2cc, 2cc + 1) -> chunk `chunk`: evaluated, split, multiplied, forgotten
+    auto embed = [&](int cc, int chunk) {
+      h16x8 ehi, elo;
+      split2(geo_embed_block(x, y, z, P.B, 2 * cc, g), geo_embed_block(x, y, z, P.B, 2 * cc + 1, g), ehi, elo);
+      mma_g3(acc, ehi, elo, ch(chunk));
+    };
+    // chunks: W0 0-2 | Fc0 3 | W1 4 | Fc1 5 | W2 6 | Fc2 7 | W3e 8-10 | W3h 11 | Fc3 12 | W4 13 | Fc4 14
+    zero<2>(acc);
+    embed(0, 0); embed(1, 1); embed(2, 2);
+    act(0); mma_g3(acc, chi, clo, ch(3));
+    next_layer();
+    mma_g3(acc, hhi, hlo, ch(4));  act(1); mma_g3(acc, chi, clo, ch(5));
+    next_layer();
+    mma_g3(acc, hhi, hlo, ch(6));  act(2); mma_g3(acc, chi, clo, ch(7));
+    next_layer();
+    embed(0, 8); embed(1, 9); embed(2, 10);
+    mma_g3(acc, hhi, hlo, ch(11)); act(3); mma_g3(acc, chi, clo, ch(12));
+    next_layer();
+    mma_g3(acc, hhi, hlo, ch(13)); act(4); mma_g3(acc, chi, clo, ch(14));
+    bad = bad | geo_output(acc, smem + kGeoFrag, P.bout, L, Q, on, raw);
+    cur = nxt;
+  }
+  report_range(bad, range_flag);
+}
+
+// ====================================================================================
+// colour decoder
+// ====================================================================================
 // Every layer is evaluated as  H'^T = W^T . H^T : the MFMA's 16 "rows" are output channels (A = weights
 // from the LDS chunk), its 16 "columns" are the wave's 16 samples (B = activations).  The D fragment
 // of lane (r = lane & 15, g = lane >> 4) then holds channels 16t + 4g + rr (t = 0..7, rr = 0..3) of
@@ -257,14 +430,108 @@ __global__ __launch_bounds__(512, 4) void mlp_geo_v3_kernel(GeoParams P, const f
 // no transposition through LDS, no activation buffer at all.  The embedding and the colour feature
 // use the same channel -> (step, slot) assignment.  LDS only holds the double-buffered weight chunk
 // (33 KB), so two workgroups share a CU and one's barriers hide behind the other's MFMAs.
+
+// The 80-feature embedding [sin p | cos p | sin v | cos v] x 20 of sample q (view direction normalised) as the five B
+// fragments of channels 16t + 4g + rr.  Phases in revolutions: the 2 pi of the reference's embedding is the period of
+// v_sin / v_cos.  (Bp / Bv as pointers: read through a reference to ColParams, the matrix loads of a wave's two sample
+// blocks are not merged - 112 loads against 76 in mlp_col_v5_kernel, and a measurable 1 %)
+__device__ __forceinline__ void col_embed(f32x4 (&e)[5], const float* Bp, const float* Bv, const float* __restrict__ pts,
+                                          const float* __restrict__ views, size_t q, int g) {
+  const float px = pts[q * 3 + 0], py = pts[q * 3 + 1], pz = pts[q * 3 + 2];
+  float vx = views[q * 3 + 0], vy = views[q * 3 + 1], vz = views[q * 3 + 2];
+  const float nrm = fmaxf(sqrtf(vx * vx + vy * vy + vz * vz), 1e-12f);
+  vx = vx / nrm; vy = vy / nrm; vz = vz / nrm;
+#pragma unroll
+  for (int t = 0; t < 5; ++t)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int f = 16 * t + 4 * g + rr;   // feature index 0..79
+      const int blk = f / 20, ff = f - blk * 20;
+      const float* Bm = blk < 2 ? Bp : Bv;
+      const float x = blk < 2 ? px : vx, y = blk < 2 ? py : vy, z = blk < 2 ? pz : vz;
+      const float a = fmaf(z, Bm[40 + ff], fmaf(y, Bm[20 + ff], x * Bm[ff]));
+      e[t][rr] = (blk & 1) ? cos_rev(a) : sin_rev(a);
+    }
+}
+
+// output layer 128 -> 3 in fp32 (A straight from global: Wout is [128][16], 3 real columns) and the sigmoid; lanes with
+// g == 0 end up with channels 0..3 of their sample.  Returns the range test of the layer's outputs
+__device__ __forceinline__ bool col_output(const f32x4 (&acc)[8], const ColParams& P, const Lane& L, int Q,
+                                           float* __restrict__ raw) {
+  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+  const float* wp = P.Wout + (4 * L.g) * 16 + L.r;
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr)
+      o = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 16], acc[t][rr], o, 0, 0, 0);
+  bool bad = false;
+  if (L.g == 0 && L.qs < Q) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      bad = bad | not_finite(o[ch]);
+      raw[(size_t)L.qs * 4 + ch] = 1.0f / (1.0f + __expf(-(o[ch] + P.bout[ch])));
+    }
+  }
+  return bad;
+}
+
+// The colour weights as the kernels stream them: 27 chunks of 32 K-rows,
+//   W0 (80 -> 96 rows) Fc0 | W1 Fc1 | W2 Fc2 | W3e (80 -> 96) W3h Fc3 | W4 Fc4.
+// CHUNK(i, operand, b): chunk i multiplies block b of the embedding (E), the hidden state (H) or the colour feature (C);
+// ACT(l): the activation of layer l, due once its pts_linears chunks are in; NEXT: the accumulators become the hidden state.
+// Layer 3 is the skip: W3e on the embedding, W3h on the hidden state.
+constexpr int kColChunks = 27;
+#define GLORIE_COL_SCHEDULE(CHUNK, ACT, NEXT)                                                                   \
+  CHUNK(0, E, 0) CHUNK(1, E, 1) CHUNK(2, E, 2) ACT(0) CHUNK(3, C, 0) NEXT                                       \
+  CHUNK(4, H, 0) CHUNK(5, H, 1) CHUNK(6, H, 2) CHUNK(7, H, 3) ACT(1) CHUNK(8, C, 0) NEXT                        \
+  CHUNK(9, H, 0) CHUNK(10, H, 1) CHUNK(11, H, 2) CHUNK(12, H, 3) ACT(2) CHUNK(13, C, 0) NEXT                    \
+  CHUNK(14, E, 0) CHUNK(15, E, 1) CHUNK(16, E, 2)                                                               \
+  CHUNK(17, H, 0) CHUNK(18, H, 1) CHUNK(19, H, 2) CHUNK(20, H, 3) ACT(3) CHUNK(21, C, 0) NEXT                   \
+  CHUNK(22, H, 0) CHUNK(23, H, 1) CHUNK(24, H, 2) CHUNK(25, H, 3) ACT(4) CHUNK(26, C, 0)
+
+// one step of the double-buffered stream: chunk cidx + 1 travels L2 -> registers while chunk cidx is multiplied out of LDS
+// buffer cidx & 1, and lands in the other buffer before the barrier.  (A macro, not a function taking three lambdas: the
+// registers that carry the next chunk stay in memory when they are captured.)
+#define GLORIE_COL_CHUNK_STEP(cidx, LOAD_NEXT, MMA, STORE_NEXT) \
+  {                                                             \
+    if ((cidx) + 1 < kColChunks) { LOAD_NEXT; }                 \
+    MMA;                                                        \
+    if ((cidx) + 1 < kColChunks) { STORE_NEXT; }                \
+    __syncthreads();                                            \
+  }
+
+// ---- exact fp32: chunks of [32][128] floats, LDS rows padded to 132 ------------------------------------------------
 constexpr int kLdw3 = 132;                  // chunk row stride in LDS (floats)
 constexpr int kChunkFloats3 = 32 * kLdw3;
 
+struct ChunkRegs { float4 a, b; };
+// thread t of 512 moves 8 floats: row = t >> 4 (0..31), cols (t & 15) * 8 .. + 7
+__device__ __forceinline__ ChunkRegs chunk_load(const float* __restrict__ Wall, int chunk) {
+  const int t = threadIdx.x;
+  const float4* src = reinterpret_cast<const float4*>(Wall + ((size_t)chunk * 32 + (t >> 4)) * 128 + (t & 15) * 8);
+  ChunkRegs r;
+  r.a = src[0];
+  r.b = src[1];
+  return r;
+}
 __device__ __forceinline__ void chunk_store3(float* Wb, const ChunkRegs& r) {
   const int t = threadIdx.x;
   float4* dst = reinterpret_cast<float4*>(Wb + (t >> 4) * kLdw3 + (t & 15) * 8);
   dst[0] = r.a;
   dst[1] = r.b;
+}
+
+// one k-step of the 128-output fp32 layers: the eight A operands are two 16-byte reads (w0, w1) of a permuted row
+__device__ __forceinline__ void mfma_step8(f32x4 (&acc)[8], const float4 w0, const float4 w1, float bv) {
+  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, bv, acc[0], 0, 0, 0);
+  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, bv, acc[1], 0, 0, 0);
+  acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, bv, acc[2], 0, 0, 0);
+  acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, bv, acc[3], 0, 0, 0);
+  acc[4] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, bv, acc[4], 0, 0, 0);
+  acc[5] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, bv, acc[5], 0, 0, 0);
+  acc[6] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, bv, acc[6], 0, 0, 0);
+  acc[7] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, bv, acc[7], 0, 0, 0);
 }
 
 // acc[to] += W[16 tt + 4g + rr][16 to + r] * b[T0 + tt][rr]  for tt < NT, rr < 4 (rows relative to the chunk).
@@ -277,19 +544,9 @@ __device__ __forceinline__ void mma_t(f32x4 (&acc)[8], const f32x4 (&b)[NB], con
 #pragma unroll
   for (int tt = 0; tt < NT; ++tt)
 #pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const float bv = b[T0 + tt][rr];
-      const float4 w0 = *reinterpret_cast<const float4*>(wp + (16 * tt + rr) * kLdw3);
-      const float4 w1 = *reinterpret_cast<const float4*>(wp + (16 * tt + rr) * kLdw3 + 64);
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, bv, acc[0], 0, 0, 0);
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, bv, acc[1], 0, 0, 0);
-      acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, bv, acc[2], 0, 0, 0);
-      acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, bv, acc[3], 0, 0, 0);
-      acc[4] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, bv, acc[4], 0, 0, 0);
-      acc[5] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, bv, acc[5], 0, 0, 0);
-      acc[6] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, bv, acc[6], 0, 0, 0);
-      acc[7] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, bv, acc[7], 0, 0, 0);
-    }
+    for (int rr = 0; rr < 4; ++rr)
+      mfma_step8(acc, *reinterpret_cast<const float4*>(wp + (16 * tt + rr) * kLdw3),
+                 *reinterpret_cast<const float4*>(wp + (16 * tt + rr) * kLdw3 + 64), b[T0 + tt][rr]);
 }
 
 __global__ __launch_bounds__(512, 4) void mlp_col_v3_kernel(ColParams P, const float* __restrict__ Wall,
@@ -299,197 +556,67 @@ __global__ __launch_bounds__(512, 4) void mlp_col_v3_kernel(ColParams P, const f
                                                             float* __restrict__ raw) {
   extern __shared__ float smem[];
   float* Wbuf = smem;                         // [2][32][132]
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const int r = lane & 15, g = lane >> 4;
-  const int q0 = blockIdx.x * kTM2;
-  const int qs = q0 + wv * 16 + r;            // this lane's sample (all four k-slots of a column share it)
-  const int q = min(qs, Q - 1);
+  const Lane L = lane_of(blockIdx.x * kTM2, Q);
+  const int g = L.g;
 
   // ---- B fragments: the embedding e (80 channels) stays in registers; the colour feature c (32
   // channels) is re-read from L2 before each of its five uses (8 registers short of 4 waves / SIMD)
   f32x4 e[5], c[2];
   auto load_c = [&]() {
+    int q = L.q;
+    asm volatile("" : "+v"(q));   // a READ each time: the compiler may not keep the eight values (or the row address) instead
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float4 v = *reinterpret_cast<const float4*>(c_col + (size_t)q * 32 + 16 * t + 4 * g);
-      c[t][0] = v.x; c[t][1] = v.y; c[t][2] = v.z; c[t][3] = v.w;
-    }
+    for (int t = 0; t < 2; ++t) c[t] = as_f32x4(*reinterpret_cast<const float4*>(c_col + (size_t)q * 32 + 16 * t + 4 * g));
   };
-  {
-    // phases in revolutions: the 2 pi of the reference's embedding is the period of v_sin / v_cos
-    const float px = pts[(size_t)q * 3 + 0], py = pts[(size_t)q * 3 + 1], pz = pts[(size_t)q * 3 + 2];
-    float vx = views[(size_t)q * 3 + 0], vy = views[(size_t)q * 3 + 1], vz = views[(size_t)q * 3 + 2];
-    const float nrm = fmaxf(sqrtf(vx * vx + vy * vy + vz * vz), 1e-12f);
-    vx = vx / nrm; vy = vy / nrm; vz = vz / nrm;
+  col_embed(e, P.Bp, P.Bv, pts, views, L.q, g);
+  // evaluated HERE, before the first chunk is requested: four waves per SIMD have 128 registers, and an embedding that the
+  // compiler interleaves with the chunk copy (60 values of Bp / Bv in flight) spills 6-10 of them (114 with both asm lines)
 #pragma unroll
-    for (int t = 0; t < 5; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int f = 16 * t + 4 * g + rr;   // feature index 0..79: [sin p | cos p | sin v | cos v] x 20
-        const int blk = f / 20, ff = f - blk * 20;
-        const float* Bm = blk < 2 ? P.Bp : P.Bv;
-        const float x = blk < 2 ? px : vx, y = blk < 2 ? py : vy, z = blk < 2 ? pz : vz;
-        const float a = fmaf(z, Bm[40 + ff], fmaf(y, Bm[20 + ff], x * Bm[ff]));
-        e[t][rr] = (blk & 1) ? cos_rev(a) : sin_rev(a);
-      }
-  }
+  for (int t = 0; t < 5; ++t) asm volatile("" : "+v"(e[t]));
 
   f32x4 acc[8], h[8];
-  constexpr int NC = 27;
   ChunkRegs nxt = chunk_load(Wall, 0);
   chunk_store3(Wbuf, nxt);
   __syncthreads();
 
-  auto act = [&](int li) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const float4 bb = *reinterpret_cast<const float4*>(P.bias + li * 128 + 16 * t + 4 * g);
-      const float4 fb = *reinterpret_cast<const float4*>(P.fcb + li * 128 + 16 * t + 4 * g);
-      acc[t][0] = softplus100_fast(acc[t][0] + bb.x) + fb.x;
-      acc[t][1] = softplus100_fast(acc[t][1] + bb.y) + fb.y;
-      acc[t][2] = softplus100_fast(acc[t][2] + bb.z) + fb.z;
-      acc[t][3] = softplus100_fast(acc[t][3] + bb.w) + fb.w;
-    }
-  };
-  auto next_layer = [&]() {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) { h[t] = acc[t]; acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  };
-
-#define GL_CHUNK(cidx, BODY)                                        \
-  {                                                                 \
-    if ((cidx) + 1 < NC) nxt = chunk_load(Wall, (cidx) + 1);        \
-    const float* Wb = Wbuf + ((cidx) & 1) * kChunkFloats3;          \
-    BODY;                                                           \
-    if ((cidx) + 1 < NC) chunk_store3(Wbuf + (((cidx) + 1) & 1) * kChunkFloats3, nxt); \
-    __syncthreads();                                                \
-  }
-
-  // layer 0: W0 (80 rows -> chunks 0..2), Fc0 (chunk 3)
+  // E / H blocks b are k-step blocks 2b, 2b + 1 (the 80-channel embedding ends with block 4)
+#define V3_MMA_E(b, Wb) mma_t<2 * (b), (b) == 2 ? 1 : 2, 5>(acc, e, Wb)
+#define V3_MMA_H(b, Wb) mma_t<2 * (b), 2, 8>(acc, h, Wb)
+#define V3_MMA_C(b, Wb) mma_t<0, 2, 2>(acc, c, Wb)
+#define V3_CHUNK(cidx, OP, b)                                                                                   \
+  GLORIE_COL_CHUNK_STEP(cidx, nxt = chunk_load(Wall, (cidx) + 1), V3_MMA_##OP(b, Wbuf + ((cidx) & 1) * kChunkFloats3), \
+                        chunk_store3(Wbuf + (((cidx) + 1) & 1) * kChunkFloats3, nxt))
+#define V3_ACT(li) load_c(); act_layer<softplus100_fast, 8, 1>(&acc, P.bias, P.fcb, li, g);
+#define V3_NEXT                                                                                       \
+  _Pragma("unroll") for (int t = 0; t < 8; ++t) { h[t] = acc[t]; acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   zero<8>(acc);
-  GL_CHUNK(0, (mma_t<0, 2, 5>(acc, e, Wb)))
-  GL_CHUNK(1, (mma_t<2, 2, 5>(acc, e, Wb)))
-  GL_CHUNK(2, (mma_t<4, 1, 5>(acc, e, Wb)))
-  load_c();
-  act(0);
-  GL_CHUNK(3, (mma_t<0, 2, 2>(acc, c, Wb)))
-  // layer 1
-  next_layer();
-  GL_CHUNK(4, (mma_t<0, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(5, (mma_t<2, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(6, (mma_t<4, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(7, (mma_t<6, 2, 8>(acc, h, Wb)))
-  load_c();
-  act(1);
-  GL_CHUNK(8, (mma_t<0, 2, 2>(acc, c, Wb)))
-  // layer 2
-  next_layer();
-  GL_CHUNK(9, (mma_t<0, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(10, (mma_t<2, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(11, (mma_t<4, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(12, (mma_t<6, 2, 8>(acc, h, Wb)))
-  load_c();
-  act(2);
-  GL_CHUNK(13, (mma_t<0, 2, 2>(acc, c, Wb)))
-  // layer 3 (skip): W3e on the embedding, W3h on the hidden state
-  next_layer();
-  GL_CHUNK(14, (mma_t<0, 2, 5>(acc, e, Wb)))
-  GL_CHUNK(15, (mma_t<2, 2, 5>(acc, e, Wb)))
-  GL_CHUNK(16, (mma_t<4, 1, 5>(acc, e, Wb)))
-  GL_CHUNK(17, (mma_t<0, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(18, (mma_t<2, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(19, (mma_t<4, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(20, (mma_t<6, 2, 8>(acc, h, Wb)))
-  load_c();
-  act(3);
-  GL_CHUNK(21, (mma_t<0, 2, 2>(acc, c, Wb)))
-  // layer 4
-  next_layer();
-  GL_CHUNK(22, (mma_t<0, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(23, (mma_t<2, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(24, (mma_t<4, 2, 8>(acc, h, Wb)))
-  GL_CHUNK(25, (mma_t<6, 2, 8>(acc, h, Wb)))
-  load_c();
-  act(4);
-  GL_CHUNK(26, (mma_t<0, 2, 2>(acc, c, Wb)))
-#undef GL_CHUNK
-  // output layer 128 -> 3 (A straight from global: Wout is [128][16], 3 real columns); lanes with g == 0
-  // end up with channels 0..3 of their sample
-  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-  {
-    const float* wp = P.Wout + (4 * g) * 16 + r;
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-        o = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 16], acc[t][rr], o, 0, 0, 0);
-  }
-  if (g == 0 && qs < Q) {
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-      raw[(size_t)qs * 4 + ch] = 1.0f / (1.0f + __expf(-(o[ch] + P.bout[ch])));
-  }
+  GLORIE_COL_SCHEDULE(V3_CHUNK, V3_ACT, V3_NEXT)
+#undef V3_NEXT
+#undef V3_ACT
+#undef V3_CHUNK
+#undef V3_MMA_C
+#undef V3_MMA_H
+#undef V3_MMA_E
+  col_output(acc, P, L, Q, raw);
 }
 
-// ---- colour decoder on the fp16 matrix cores with fp32 accuracy (3-term split) -------------------------------------
-// The fp32 MFMA (16x16x4, 64 flops per cycle and SIMD) is the slowest matrix path of the chip; the fp16 one (16x16x32) is
-// 16x faster.  Every weight and activation is split as x = hi + lo (hi = fp16(x), lo = fp16(x - hi): 22 mantissa bits) and
-// a product is accumulated as hi*hi + hi*lo + lo*hi in fp32 - the dropped lo*lo term is 2^-22 relative, the fp16 products
-// are exact in the fp32 accumulator - so a 32-row chunk costs 3 x 8 MFMAs of 16 cycles instead of 64 of 32.  The
-// transposed formulation carries over: the accumulator blocks (2t, 2t+1) of a layer, split and packed, are the eight
-// k-slots of a lane's B operand for chunk t of the next layer (slot s <-> chunk row 16 (s >> 2) + 4 g + (s & 3), the same
-// row order as the fp32 chunks); the weights are packed once per chunk as A fragments
-// [hi|lo][out block 8][lane 64][8 halfs] (point_ops.pack_decoders) and streamed through LDS as they are (linear copy,
-// conflict-free ds_read_b128).  Softplus, biases and the 128 -> 3 output layer stay fp32 as in mlp_col_v3_kernel.
-typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;
+// ---- 3-term split: chunks of 4096 floats = [hi|lo][out block 8][lane 64][8 halfs], NB column blocks per wave ----------
+// Round 2's colour kernel (removed in round 4) gave a wave 16 samples: every A fragment (weights) read from LDS feeds 3
+// MFMAs, and the 442 KB weight stream is re-staged for every 128 samples - LDS reads (1 KB per 3 x 16 MFMA cycles and wave:
+// 1024 LDS cycles against 768 matrix cycles per chunk and CU) and the L2 -> LDS stream (2.1 GB per 614k-sample batch) bound
+// it, not the matrix pipe (MfmaUtil 41 %).  Here a wave owns NB = 2 blocks of 16 samples: an A fragment feeds 6 MFMAs, a
+// workgroup of WAVES waves covers 32 WAVES samples per staged chunk, and the second block's vector work (softplus, splits)
+// overlaps the first one's MFMAs inside the same wave.  Same packed weights, same arithmetic per sample (bit-identical
+// results to that kernel).  Launched as <2, 4>: measured per 614k-sample batch against 16 samples per wave and against
+// 8-wave workgroups, 427 vs 495 / 485 us (the other two forms were removed in round 4).
+//
+// Round 6, measured and not kept: three waves per SIMD instead of two (236 -> 168 registers: the embedding formed where it is
+// consumed, the colour feature re-read before each use, the weight chunk L2 -> LDS by DMA instead of through 16 VGPRs, layer 3
+// with its hidden chunks first) - 0.858-0.860 ms for the three decoder kernels against 0.838-0.853 ms, frame 5.49 / 5.63 against
+// 5.47 / 5.61 ms in interleaved runs (tools/time_mlp.py): like every occupancy change tried on these kernels, no gain.  (The
+// first build also failed the fixture test - a wrong chunk order in the re-ordered layer - and was not debugged further.)
 constexpr int kChunkFloats16 = 4096;          // 2 x 8 x 64 x 8 halfs
 
-__device__ __forceinline__ ChunkRegs chunk_load16(const float* __restrict__ W16, int chunk) {
-  const float4* src = reinterpret_cast<const float4*>(W16 + (size_t)chunk * kChunkFloats16 + threadIdx.x * 8);
-  ChunkRegs r;
-  r.a = src[0];
-  r.b = src[1];
-  return r;
-}
-__device__ __forceinline__ void chunk_store16(float* Wb, const ChunkRegs& r) {
-  float4* dst = reinterpret_cast<float4*>(Wb + threadIdx.x * 8);
-  dst[0] = r.a;
-  dst[1] = r.b;
-}
-// split two accumulator blocks (channels 4g + rr of block 0 -> slots 0..3, of block 1 -> slots 4..7) into hi / lo halfs
-__device__ __forceinline__ void split2(const f32x4 a, const f32x4 b, h16x8& hi, h16x8& lo) {
-  const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    hi[s] = (_Float16)v[s];
-#ifdef EXP_MLP_NO_SPLIT
-    lo[s] = (_Float16)0.0f;                                 // ablation: the cost of forming the low halves
-#else
-    lo[s] = (_Float16)(v[s] - (float)hi[s]);
-#endif
-  }
-}
-// Range guard of the split kernels.  The split holds |x| <= 65504 (fp16 max).  A larger operand becomes hi = inf,
-// lo = x - inf = -inf, and its products a.hi * inf + a.hi * (-inf) are NaN in EVERY output channel it feeds; softplus, the
-// (NaN-keeping) ReLU below, the biases, the next split and the fp32 output layers all pass a NaN on, so an overflow anywhere
-// in a network surfaces as a non-finite value at its output.  The kernels therefore test only what they are about to store
-// (a handful of values per lane - tracking max |x| at every split costs ~100 registers' worth of spills in the colour
-// kernel) and raise the caller's flag; the host then repeats the call on the exact-fp32 MFMA kernels.  (Small magnitudes are
-// safe: below 2^-3 the low half falls into fp16 subnormals and the split's error becomes ABSOLUTE, 2^-25 per operand.)
-__device__ __forceinline__ bool not_finite(float x) { return !(__builtin_fabsf(x) <= 3.0e38f); }
-__device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.0f ? 0.0f : x; }
-__device__ __forceinline__ void report_range(bool bad, int* __restrict__ range_flag) {
-  if (range_flag && __builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(range_flag, 1);
-}
-
-
-// ---- colour decoder, round 3: NB column blocks (16 NB samples) per wave ------------------------------------------------
-// Round 2's colour kernel (mlp_col_v4_kernel, removed in round 4) gave a wave 16 samples: every A fragment (weights) read from LDS feeds 3 MFMAs, and the 442 KB weight
-// stream is re-staged for every 128 samples - LDS reads (1 KB per 3 x 16 MFMA cycles and wave: 1024 LDS cycles against 768
-// matrix cycles per chunk and CU) and the L2 -> LDS stream (2.1 GB per 614k-sample batch) bound it, not the matrix pipe
-// (MfmaUtil 41 %).  Here a wave owns NB = 2 blocks of 16 samples: an A fragment feeds 6 MFMAs, a workgroup of WAVES waves
-// covers 32 WAVES samples per staged chunk, and the second block's vector work (softplus, splits) overlaps the first one's
-// MFMAs inside the same wave.  Same packed weights, same arithmetic per sample (bit-identical results to v4).
 template <int THREADS>
 __device__ __forceinline__ void chunk_copy16(const float* __restrict__ W16, int chunk, float4 (&regs)[4096 / 4 / THREADS]) {
   const float4* src = reinterpret_cast<const float4*>(W16 + (size_t)chunk * kChunkFloats16);
@@ -511,19 +638,10 @@ __device__ __forceinline__ void mma_h3n(f32x4 (&acc)[NB][8], const h16x8 (&bhi)[
   for (int to = 0; to < 8; ++to) {
     const h16x8 ahi = wp[to * 64], alo = wp[(8 + to) * 64];
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      acc[nb][to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi[nb], acc[nb][to], 0, 0, 0);
-      acc[nb][to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo[nb], acc[nb][to], 0, 0, 0);
-      acc[nb][to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi[nb], acc[nb][to], 0, 0, 0);
-    }
+    for (int nb = 0; nb < NB; ++nb) acc[nb][to] = mfma_h3(ahi, alo, bhi[nb], blo[nb], acc[nb][to]);
   }
 }
 
-// Round 6, measured and not kept: three waves per SIMD instead of two (236 -> 168 registers: the embedding formed where it is
-// consumed, the colour feature re-read before each use, the weight chunk L2 -> LDS by DMA instead of through 16 VGPRs, layer 3
-// with its hidden chunks first) - 0.858-0.860 ms for the three decoder kernels against 0.838-0.853 ms, frame 5.49 / 5.63 against
-// 5.47 / 5.61 ms in interleaved runs (tools/time_mlp.py): like every occupancy change tried on these kernels, no gain.  (The
-// first build also failed the fixture test - a wrong chunk order in the re-ordered layer - and was not debugged further.)
 template <int NB, int WAVES>
 __global__ __launch_bounds__(WAVES * 64, NB == 1 ? 4 : 2)
 void mlp_col_v5_kernel(ColParams P, const float* __restrict__ W16, const float* __restrict__ pts,
@@ -533,148 +651,179 @@ void mlp_col_v5_kernel(ColParams P, const float* __restrict__ W16, const float* 
   constexpr int THREADS = WAVES * 64;
   extern __shared__ float smem[];
   float* Wbuf = smem;                         // [2][4096]
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const int r = lane & 15, g = lane >> 4;
-  const int q0 = blockIdx.x * (WAVES * 16 * NB);
-  int qs[NB], q[NB];
+  Lane L[NB];
 #pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    qs[nb] = q0 + (wv * NB + nb) * 16 + r;    // this lane's sample of block nb (all four k-slots of a column share it)
-    q[nb] = min(qs[nb], Q - 1);
-  }
+  for (int nb = 0; nb < NB; ++nb) L[nb] = lane_of(blockIdx.x * (WAVES * 16 * NB), Q, NB, nb);
+  const int g = L[0].g;
   h16x8 ehi[3][NB], elo[3][NB], chi[NB], clo[NB];
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
-    const size_t qq = (size_t)q[nb];
-    const float px = pts[qq * 3 + 0], py = pts[qq * 3 + 1], pz = pts[qq * 3 + 2];
-    float vx = views[qq * 3 + 0], vy = views[qq * 3 + 1], vz = views[qq * 3 + 2];
-    const float nrm = fmaxf(sqrtf(vx * vx + vy * vy + vz * vz), 1e-12f);
-    vx = vx / nrm; vy = vy / nrm; vz = vz / nrm;
-    f32x4 e[6];
-#pragma unroll
-    for (int t = 0; t < 5; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int f = 16 * t + 4 * g + rr;   // feature index 0..79: [sin p | cos p | sin v | cos v] x 20
-        const int blk = f / 20, ff = f - blk * 20;
-        const float* Bm = blk < 2 ? P.Bp : P.Bv;
-        const float x = blk < 2 ? px : vx, y = blk < 2 ? py : vy, z = blk < 2 ? pz : vz;
-        const float a = fmaf(z, Bm[40 + ff], fmaf(y, Bm[20 + ff], x * Bm[ff]));
-        e[t][rr] = (blk & 1) ? cos_rev(a) : sin_rev(a);
-      }
-    e[5] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) split2(e[2 * c], e[2 * c + 1], ehi[c][nb], elo[c][nb]);
+    const size_t qq = (size_t)L[nb].q;
+    f32x4 e[5];
+    col_embed(e, P.Bp, P.Bv, pts, views, qq, g);
+    // (the sixth block of the third chunk is zero: 80 channels)
+    split2(e[0], e[1], ehi[0][nb], elo[0][nb]);
+    split2(e[2], e[3], ehi[1][nb], elo[1][nb]);
+    split2(e[4], f32x4{0.f, 0.f, 0.f, 0.f}, ehi[2][nb], elo[2][nb]);
     const float4 v0 = *reinterpret_cast<const float4*>(c_col + qq * 32 + 4 * g);
     const float4 v1 = *reinterpret_cast<const float4*>(c_col + qq * 32 + 16 + 4 * g);
-    split2(f32x4{v0.x, v0.y, v0.z, v0.w}, f32x4{v1.x, v1.y, v1.z, v1.w}, chi[nb], clo[nb]);
+    split2(as_f32x4(v0), as_f32x4(v1), chi[nb], clo[nb]);
   }
 
   f32x4 acc[NB][8];
   h16x8 hhi[4][NB], hlo[4][NB];
-  constexpr int NC = 27;
   float4 nxt[4096 / 4 / THREADS];
   chunk_copy16<THREADS>(W16, 0, nxt);
   chunk_put16<THREADS>(Wbuf, nxt);
   __syncthreads();
 
-  auto act = [&](int li) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const float4 bb = *reinterpret_cast<const float4*>(P.bias + li * 128 + 16 * t + 4 * g);
-      const float4 fb = *reinterpret_cast<const float4*>(P.fcb + li * 128 + 16 * t + 4 * g);
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        acc[nb][t][0] = softplus100_fast(acc[nb][t][0] + bb.x) + fb.x;
-        acc[nb][t][1] = softplus100_fast(acc[nb][t][1] + bb.y) + fb.y;
-        acc[nb][t][2] = softplus100_fast(acc[nb][t][2] + bb.z) + fb.z;
-        acc[nb][t][3] = softplus100_fast(acc[nb][t][3] + bb.w) + fb.w;
-      }
-    }
-  };
-  auto next_layer = [&]() {
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) split2(acc[nb][2 * c], acc[nb][2 * c + 1], hhi[c][nb], hlo[c][nb]);
-      zero<8>(acc[nb]);
-    }
-  };
-
-#define GL_CHUNK(cidx, BHI, BLO)                                    \
-  {                                                                 \
-    if ((cidx) + 1 < NC) chunk_copy16<THREADS>(W16, (cidx) + 1, nxt); \
-    mma_h3n<NB>(acc, BHI, BLO, Wbuf + ((cidx) & 1) * kChunkFloats16); \
-    if ((cidx) + 1 < NC) chunk_put16<THREADS>(Wbuf + (((cidx) + 1) & 1) * kChunkFloats16, nxt); \
-    __syncthreads();                                                \
+#define V5_B_E(b) ehi[b], elo[b]
+#define V5_B_H(b) hhi[b], hlo[b]
+#define V5_B_C(b) chi, clo
+#define V5_CHUNK(cidx, OP, b)                                                                                   \
+  GLORIE_COL_CHUNK_STEP(cidx, chunk_copy16<THREADS>(W16, (cidx) + 1, nxt),                                      \
+                        mma_h3n<NB>(acc, V5_B_##OP(b), Wbuf + ((cidx) & 1) * kChunkFloats16),                   \
+                        chunk_put16<THREADS>(Wbuf + (((cidx) + 1) & 1) * kChunkFloats16, nxt))
+#define V5_ACT(li) act_layer<softplus100_fast, 8, NB>(acc, P.bias, P.fcb, li, g);
+#define V5_NEXT                                                                                       \
+  _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) {                                                 \
+    _Pragma("unroll") for (int c = 0; c < 4; ++c) split2(acc[nb][2 * c], acc[nb][2 * c + 1], hhi[c][nb], hlo[c][nb]); \
+    zero<8>(acc[nb]);                                                                                 \
   }
-
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) zero<8>(acc[nb]);
-  GL_CHUNK(0, ehi[0], elo[0])
-  GL_CHUNK(1, ehi[1], elo[1])
-  GL_CHUNK(2, ehi[2], elo[2])
-  act(0);
-  GL_CHUNK(3, chi, clo)
-  next_layer();
-  GL_CHUNK(4, hhi[0], hlo[0])
-  GL_CHUNK(5, hhi[1], hlo[1])
-  GL_CHUNK(6, hhi[2], hlo[2])
-  GL_CHUNK(7, hhi[3], hlo[3])
-  act(1);
-  GL_CHUNK(8, chi, clo)
-  next_layer();
-  GL_CHUNK(9, hhi[0], hlo[0])
-  GL_CHUNK(10, hhi[1], hlo[1])
-  GL_CHUNK(11, hhi[2], hlo[2])
-  GL_CHUNK(12, hhi[3], hlo[3])
-  act(2);
-  GL_CHUNK(13, chi, clo)
-  next_layer();                               // layer 3 (skip): W3e on the embedding, W3h on the hidden state
-  GL_CHUNK(14, ehi[0], elo[0])
-  GL_CHUNK(15, ehi[1], elo[1])
-  GL_CHUNK(16, ehi[2], elo[2])
-  GL_CHUNK(17, hhi[0], hlo[0])
-  GL_CHUNK(18, hhi[1], hlo[1])
-  GL_CHUNK(19, hhi[2], hlo[2])
-  GL_CHUNK(20, hhi[3], hlo[3])
-  act(3);
-  GL_CHUNK(21, chi, clo)
-  next_layer();
-  GL_CHUNK(22, hhi[0], hlo[0])
-  GL_CHUNK(23, hhi[1], hlo[1])
-  GL_CHUNK(24, hhi[2], hlo[2])
-  GL_CHUNK(25, hhi[3], hlo[3])
-  act(4);
-  GL_CHUNK(26, chi, clo)
-#undef GL_CHUNK
-  // output layer 128 -> 3 in fp32 as in mlp_col_v3_kernel
+  GLORIE_COL_SCHEDULE(V5_CHUNK, V5_ACT, V5_NEXT)
+#undef V5_NEXT
+#undef V5_ACT
+#undef V5_CHUNK
+#undef V5_B_C
+#undef V5_B_H
+#undef V5_B_E
 #pragma unroll
-  for (int nb = 0; nb < NB; ++nb) {
-    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* wp = P.Wout + (4 * g) * 16 + r;
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-        o = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 16], acc[nb][t][rr], o, 0, 0, 0);
-    if (g == 0 && qs[nb] < Q) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        bad = bad | not_finite(o[ch]);
-        raw[(size_t)qs[nb] * 4 + ch] = 1.0f / (1.0f + __expf(-(o[ch] + P.bout[ch])));
-      }
-    }
-  }
+  for (int nb = 0; nb < NB; ++nb) bad = bad | col_output(acc[nb], P, L[nb], Q, raw);
   report_range(bad, range_flag);
 }
 
-// per-neighbour F_theta, transposed formulation (see mlp_col_v3_kernel): W1 (52 x 128) resident in LDS with
-// the permuted column order, the 52 input channels of neighbour k built directly as B fragments - lane
-// (r, g) owns sample r and supplies, for k-slot g, colour-feature channels 16t + 4g + rr (two 16-byte loads
-// of the neighbour's feature row) and embedding features 4s + g (s = 0..4; sin for feature < 10, cos
-// otherwise).  No staging buffer and no barrier inside the neighbour loop; the weighted sum of the eight
+// ====================================================================================
+// per-neighbour F_theta
+// ====================================================================================
+// Transposed formulation (see mlp_col_v3_kernel): W1 (52 x 128) resident in LDS, the 52 input channels of neighbour k
+// built directly as B fragments - lane (r, g) owns sample r and supplies, for k-slot g, colour-feature channels
+// 16t + 4g + rr (two 16-byte loads of the neighbour's feature row) and embedding features 4s + g (s = 0..4; sin for
+// feature < 10, cos otherwise).  No staging buffer and no barrier inside the neighbour loop; the weighted sum of the eight
 // softplus outputs stays in the accumulator layout, which is again the B layout of the second layer.
+
+// LDS of a workgroup: the kernel's form of W1 (WFLOATS floats), then what both kernels share
+struct NbLds {
+  float* b1s;     // [128]
+  float* wbuf;    // [128][8] IDW weights (0 for an absent neighbour)
+  int* ibuf;      // [128][8] neighbour ids (0 for an absent one)
+  float* bs;      // [20][4] B[:, f mod 10] (revolutions per metre): 15 registers short otherwise
+};
+constexpr size_t nb_lds_bytes(int wfloats) {
+  return sizeof(float) * (wfloats + 128 + kTM2 * 8 + 80) + sizeof(int) * kTM2 * 8;
+}
+__device__ __forceinline__ NbLds nb_lds(float* smem, int wfloats) {
+  NbLds s;
+  s.b1s = smem + wfloats;
+  s.wbuf = s.b1s + 128;
+  s.ibuf = reinterpret_cast<int*>(s.wbuf + kTM2 * 8);
+  s.bs = reinterpret_cast<float*>(s.ibuf + kTM2 * 8);
+  return s;
+}
+constexpr int kNbW1Lds = 52 * kLdw3;          // exact kernel: [52][132], columns permuted like the colour chunks
+constexpr int kNbFrag = 8192;                 // split kernel: [2 chunks][hi|lo][8][64] fragments of 8 halfs = 32 KB
+
+// frequency vectors, IDW weights and neighbour ids of the workgroup's 128 samples (from sample q0) into LDS
+__device__ __forceinline__ void nb_stage_meta(const NbLds& s, const float* __restrict__ B, const int64_t* __restrict__ I,
+                                              const float* __restrict__ wts, int q0, int Q) {
+  const int tid = threadIdx.x;
+  if (tid < 80) {
+    const int f = tid >> 2, d = tid & 3;
+    s.bs[tid] = d < 3 ? B[d * 10 + (f < 10 ? f : f - 10)] : 0.0f;
+  }
+  for (int idx = tid; idx < kTM2 * 8; idx += 512) {
+    const int row = idx >> 3;
+    const int q = min(q0 + row, Q - 1);
+    const int ii = (int)I[(size_t)q * 8 + (idx & 7)];
+    s.wbuf[idx] = (q0 + row < Q && ii >= 0) ? wts[(size_t)q * 8 + (idx & 7)] : 0.0f;
+    s.ibuf[idx] = ii < 0 ? 0 : ii;
+  }
+}
+
+// neighbour k of the lane's sample: IDW weight, the two 16-byte pieces of its colour-feature row this lane supplies, and its
+// position relative to the sample at (qx, qy, qz)
+struct NbRow { float w; float4 c0, c1; float rx, ry, rz; };
+__device__ __forceinline__ NbRow nb_row(const NbLds& s, int srow, int k, const float* __restrict__ cloud,
+                                        const float* __restrict__ col_feats, int g, float qx, float qy, float qz, int qs) {
+#ifdef EXP_NB_NO_GATHER
+  const int pt = qs & 0xffff;                               // ablation: consecutive rows instead of the neighbours'
+#else
+  const int pt = s.ibuf[srow * 8 + k];
+#endif
+  NbRow n;
+  n.w = s.wbuf[srow * 8 + k];
+  n.c0 = *reinterpret_cast<const float4*>(col_feats + (size_t)pt * 32 + 4 * g);
+  n.c1 = *reinterpret_cast<const float4*>(col_feats + (size_t)pt * 32 + 16 + 4 * g);
+  n.rx = cloud[(size_t)pt * 3 + 0] - qx; n.ry = cloud[(size_t)pt * 3 + 1] - qy; n.rz = cloud[(size_t)pt * 3 + 2] - qz;
+  return n;
+}
+// embedding feature 4 sidx + g of the relative position: frequency column (f mod 10), sin for f < 10; phases in revolutions
+__device__ __forceinline__ float nb_embed(const NbRow& n, const float* bsl, int sidx, int g) {
+  const float4 bf = *reinterpret_cast<const float4*>(bsl + 16 * sidx);
+  const float a = fmaf(n.rz, bf.z, fmaf(n.ry, bf.y, n.rx * bf.x));
+#ifdef EXP_NB_NO_SINCOS
+  return a;
+#else
+  return (4 * sidx + g >= 10) ? cos_rev(a) : sin_rev(a);
+#endif
+}
+
+// ysum += w softplus(acc + b1): one neighbour's first-layer output into the IDW sum
+__device__ __forceinline__ void nb_accumulate(f32x4 (&ysum)[8], const f32x4 (&acc)[8], float w, const float* b1s, int g) {
+#pragma unroll
+  for (int t = 0; t < 8; ++t) {
+    const float4 bb = *reinterpret_cast<const float4*>(b1s + 16 * t + 4 * g);
+    ysum[t][0] += w * softplus100_fast(acc[t][0] + bb.x);
+    ysum[t][1] += w * softplus100_fast(acc[t][1] + bb.y);
+    ysum[t][2] += w * softplus100_fast(acc[t][2] + bb.z);
+    ysum[t][3] += w * softplus100_fast(acc[t][3] + bb.w);
+  }
+}
+
+// second layer 128 -> 32 in fp32 on the IDW sum (A = W2 straight from global / L2, 16 KB shared by everybody), + b2 sw, and
+// the store of the sample's colour feature (0 without neighbours).  Returns the range test of what was stored
+__device__ __forceinline__ bool nb_finish(const f32x4 (&ysum)[8], float sw, const NbParams& P, const Lane& L, int Q,
+                                          const uint8_t* __restrict__ has, float* __restrict__ c_col) {
+  const int g = L.g;
+  f32x4 o[2];
+  zero<2>(o);
+  const float* wp = P.W2 + (4 * g) * 32 + L.r;
+#pragma unroll
+  for (int t = 0; t < 8; ++t)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      o[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 32], ysum[t][rr], o[0], 0, 0, 0);
+      o[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 32 + 16], ysum[t][rr], o[1], 0, 0, 0);
+    }
+  bool bad = false;
+  if (L.qs < Q) {
+    const bool h = has[L.qs] != 0;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const float4 b2 = *reinterpret_cast<const float4*>(P.b2 + 16 * t + 4 * g);
+      float4 v;
+      v.x = h ? o[t][0] + b2.x * sw : 0.0f;
+      v.y = h ? o[t][1] + b2.y * sw : 0.0f;
+      v.z = h ? o[t][2] + b2.z * sw : 0.0f;
+      v.w = h ? o[t][3] + b2.w * sw : 0.0f;
+      bad = bad | not_finite(v.x + v.y + v.z + v.w);
+      *reinterpret_cast<float4*>(c_col + (size_t)L.qs * 32 + 16 * t + 4 * g) = v;
+    }
+  }
+  return bad;
+}
+
 __global__ __launch_bounds__(512, 4) void mlp_nb_v3_kernel(NbParams P, const float* __restrict__ pts,
                                                            const float* __restrict__ cloud,
                                                            const float* __restrict__ col_feats,
@@ -683,38 +832,22 @@ __global__ __launch_bounds__(512, 4) void mlp_nb_v3_kernel(NbParams P, const flo
                                                            const uint8_t* __restrict__ has, int Q,
                                                            float* __restrict__ c_col) {
   extern __shared__ float smem[];
-  float* W1s = smem;                          // [52][132], columns permuted like the colour chunks
-  float* b1s = W1s + 52 * kLdw3;              // [128]
-  float* wbuf = b1s + 128;                    // [128][8] IDW weights (0 for an absent neighbour)
-  int* ibuf = reinterpret_cast<int*>(wbuf + kTM2 * 8);  // [128][8] neighbour ids (0 for an absent one)
-  float* bs = reinterpret_cast<float*>(ibuf + kTM2 * 8);  // [20][4] B[:, f mod 10] (revolutions per metre)
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const int r = lane & 15, g = lane >> 4;
+  float* W1s = smem;
+  const NbLds s = nb_lds(smem, kNbW1Lds);
+  const int tid = threadIdx.x;
   const int q0 = blockIdx.x * kTM2;
-  if (tid < 80) {
-    const int f = tid >> 2, d = tid & 3;
-    bs[tid] = d < 3 ? P.B[d * 10 + (f < 10 ? f : f - 10)] : 0.0f;
-  }
   for (int idx = tid; idx < 52 * 128; idx += 512) {
     const int col = idx & 127, to = col >> 4, rc = col & 15;
     W1s[(idx >> 7) * kLdw3 + (to >> 2) * 64 + rc * 4 + (to & 3)] = P.W1[idx];
   }
-  if (tid < 128) b1s[tid] = P.b1[tid];
-  for (int idx = tid; idx < kTM2 * 8; idx += 512) {
-    const int row = idx >> 3;
-    const int q = min(q0 + row, Q - 1);
-    const int ii = (int)I[(size_t)q * 8 + (idx & 7)];
-    wbuf[idx] = (q0 + row < Q && ii >= 0) ? wts[(size_t)q * 8 + (idx & 7)] : 0.0f;
-    ibuf[idx] = ii < 0 ? 0 : ii;
-  }
+  if (tid < 128) s.b1s[tid] = P.b1[tid];
+  nb_stage_meta(s, P.B, I, wts, q0, Q);
   __syncthreads();
-  const int srow = wv * 16 + r;               // this lane's sample row inside the workgroup
-  const int qs = q0 + srow;
-  const int q = min(qs, Q - 1);
-  const float qx = pts[(size_t)q * 3 + 0], qy = pts[(size_t)q * 3 + 1], qz = pts[(size_t)q * 3 + 2];
-  // embedding features of this lane: f = 4s + g; frequency column (f mod 10), sin for f < 10.  The
-  // frequency vectors sit in LDS as [20][4] (15 registers short otherwise); phases in revolutions.
-  const float* bsl = bs + 4 * g;
+  const Lane L = lane_of(q0, Q);
+  const int r = L.r, g = L.g;
+  const int srow = L.wv * 16 + r;             // this lane's sample row inside the workgroup
+  const float qx = pts[(size_t)L.q * 3 + 0], qy = pts[(size_t)L.q * 3 + 1], qz = pts[(size_t)L.q * 3 + 2];
+  const float* bsl = s.bs + 4 * g;
   f32x4 ysum[8];
   zero<8>(ysum);
   float sw = 0.0f;
@@ -722,12 +855,7 @@ __global__ __launch_bounds__(512, 4) void mlp_nb_v3_kernel(NbParams P, const flo
   const float* wpc = W1s + (20 + 4 * g) * kLdw3 + r * 4;    // colour-feature rows 20 + 16t + 4g + rr
 #pragma unroll 1
   for (int k = 0; k < 8; ++k) {
-    const int pt = ibuf[srow * 8 + k];
-    const float w = wbuf[srow * 8 + k];
-    const float4 c0 = *reinterpret_cast<const float4*>(col_feats + (size_t)pt * 32 + 4 * g);
-    const float4 c1 = *reinterpret_cast<const float4*>(col_feats + (size_t)pt * 32 + 16 + 4 * g);
-    const float rx = cloud[(size_t)pt * 3 + 0] - qx, ry = cloud[(size_t)pt * 3 + 1] - qy,
-                rz = cloud[(size_t)pt * 3 + 2] - qz;
+    const NbRow n = nb_row(s, srow, k, cloud, col_feats, g, qx, qy, qz, L.qs);
     f32x4 acc[8];
     zero<8>(acc);
     // 13 k-steps, software pipelined by hand: the two 16-byte weight reads of step i + 1 are issued before
@@ -740,423 +868,58 @@ __global__ __launch_bounds__(512, 4) void mlp_nb_v3_kernel(NbParams P, const flo
       const float4 w0 = w0n, w1 = w1n;                                                   \
       const float bv = (BV);                                                             \
       NEXT                                                                               \
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, bv, acc[0], 0, 0, 0);          \
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, bv, acc[1], 0, 0, 0);          \
-      acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, bv, acc[2], 0, 0, 0);          \
-      acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, bv, acc[3], 0, 0, 0);          \
-      acc[4] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, bv, acc[4], 0, 0, 0);          \
-      acc[5] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, bv, acc[5], 0, 0, 0);          \
-      acc[6] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, bv, acc[6], 0, 0, 0);          \
-      acc[7] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, bv, acc[7], 0, 0, 0);          \
+      mfma_step8(acc, w0, w1, bv);                                                       \
       __builtin_amdgcn_sched_barrier(0);                                                 \
     }
     float4 w0n, w1n;
     NB_LOAD(wpe)
 #pragma unroll
     for (int sidx = 0; sidx < 5; ++sidx) {
-      const float4 bf = *reinterpret_cast<const float4*>(bsl + 16 * sidx);
-      const float a = fmaf(rz, bf.z, fmaf(ry, bf.y, rx * bf.x));
-      const float ev = (4 * sidx + g >= 10) ? cos_rev(a) : sin_rev(a);
+      const float ev = nb_embed(n, bsl, sidx, g);
       if (sidx < 4) NB_STEP(ev, NB_LOAD(wpe + 4 * (sidx + 1) * kLdw3))
       else NB_STEP(ev, NB_LOAD(wpc))
     }
-    NB_STEP(c0.x, NB_LOAD(wpc + 1 * kLdw3))
-    NB_STEP(c0.y, NB_LOAD(wpc + 2 * kLdw3))
-    NB_STEP(c0.z, NB_LOAD(wpc + 3 * kLdw3))
-    NB_STEP(c0.w, NB_LOAD(wpc + 16 * kLdw3))
-    NB_STEP(c1.x, NB_LOAD(wpc + 17 * kLdw3))
-    NB_STEP(c1.y, NB_LOAD(wpc + 18 * kLdw3))
-    NB_STEP(c1.z, NB_LOAD(wpc + 19 * kLdw3))
-    NB_STEP(c1.w, )
+    NB_STEP(n.c0.x, NB_LOAD(wpc + 1 * kLdw3))
+    NB_STEP(n.c0.y, NB_LOAD(wpc + 2 * kLdw3))
+    NB_STEP(n.c0.z, NB_LOAD(wpc + 3 * kLdw3))
+    NB_STEP(n.c0.w, NB_LOAD(wpc + 16 * kLdw3))
+    NB_STEP(n.c1.x, NB_LOAD(wpc + 17 * kLdw3))
+    NB_STEP(n.c1.y, NB_LOAD(wpc + 18 * kLdw3))
+    NB_STEP(n.c1.z, NB_LOAD(wpc + 19 * kLdw3))
+    NB_STEP(n.c1.w, )
 #undef NB_STEP
 #undef NB_LOAD
-    sw += w;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const float4 bb = *reinterpret_cast<const float4*>(b1s + 16 * t + 4 * g);
-      ysum[t][0] += w * softplus100_fast(acc[t][0] + bb.x);
-      ysum[t][1] += w * softplus100_fast(acc[t][1] + bb.y);
-      ysum[t][2] += w * softplus100_fast(acc[t][2] + bb.z);
-      ysum[t][3] += w * softplus100_fast(acc[t][3] + bb.w);
-    }
+    sw += n.w;
+    nb_accumulate(ysum, acc, n.w, s.b1s, g);
   }
-  // second layer 128 -> 32 (A = W2 straight from global / L2, 16 KB shared by everybody)
-  f32x4 o[2];
-  zero<2>(o);
-  {
-    const float* wp = P.W2 + (4 * g) * 32 + r;
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        o[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 32], ysum[t][rr], o[0], 0, 0, 0);
-        o[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 32 + 16], ysum[t][rr], o[1], 0, 0, 0);
-      }
-  }
-  if (qs < Q) {
-    const bool h = has[qs] != 0;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float4 b2 = *reinterpret_cast<const float4*>(P.b2 + 16 * t + 4 * g);
-      float4 v;
-      v.x = h ? o[t][0] + b2.x * sw : 0.0f;
-      v.y = h ? o[t][1] + b2.y * sw : 0.0f;
-      v.z = h ? o[t][2] + b2.z * sw : 0.0f;
-      v.w = h ? o[t][3] + b2.w * sw : 0.0f;
-      *reinterpret_cast<float4*>(c_col + (size_t)qs * 32 + 16 * t + 4 * g) = v;
-    }
-  }
+  nb_finish(ysum, sw, P, L, Q, has, c_col);
 }
 
-// geometry decoder on the fp16 matrix cores with the 3-term split (see mlp_col_v5_kernel): the 480 K-rows are 15 chunks
-// of 32, packed by point_ops.pack_decoders as A fragments [chunk][hi|lo][out block 2][lane 64][8 halfs] (1024 floats per
-// chunk) and staged once per workgroup; the 32 -> 1 output layer stays fp32.  The 96-channel embedding is evaluated where
-// it is consumed (layer 0 and again at the skip layer) instead of being kept: 24 v_sin per sample against 24 registers
-// that the 128-register budget of four waves per SIMD does not have.
-constexpr int kGeoFrag = 15 * 1024;            // floats
-
-__device__ __forceinline__ void mma_g3(f32x4 (&acc)[2], const h16x8 bhi, const h16x8 blo, const float* chunk) {
-  const h16x8* wp = reinterpret_cast<const h16x8*>(chunk) + (threadIdx.x & 63);
+// one 32-slot chunk of the split kernel's first layer: fragments FRAG0 .. FRAG0 + 15 of W1 ([hi 8 | lo 8] output blocks)
+template <int FRAG0>
+__device__ __forceinline__ void nb_chunk_h3(f32x4 (&acc)[8], const h16x8 bhi, const h16x8 blo, const h16x8* wl) {
 #pragma unroll
-  for (int to = 0; to < 2; ++to) {
-    const h16x8 ahi = wp[to * 64], alo = wp[(2 + to) * 64];
-    acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc[to], 0, 0, 0);
-    acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc[to], 0, 0, 0);
-    acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc[to], 0, 0, 0);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// GO (gather only): the measurement instantiation behind stage_flags bit 2 of glorie_render_mlp - the kernel's R2 phase
-// alone (ids, weights, the 8 feature rows and their interpolation) with the decoder removed, so that bench.py can time the
-// feature pull AS THE PRODUCT PERFORMS IT (inside this kernel, not in a stand-alone gather launch) in its own process.
-template <bool GO>
-__global__ __launch_bounds__(512, 4) void mlp_geo_v4_kernel(GeoParams P, const float* __restrict__ frags,
-                                                            const float* __restrict__ wout,
-                                                            const float* __restrict__ pts,
-                                                            const float* __restrict__ c_geo,
-                                                            const float* __restrict__ geo_feats,
-                                                            const int64_t* __restrict__ I,
-                                                            const float* __restrict__ wts,
-                                                            const uint8_t* __restrict__ has, int Q,
-                                                            float* __restrict__ raw, int* __restrict__ range_flag) {
-  bool bad = false;
-  extern __shared__ float smem[];              // [15][1024] fragments | [32][16] output layer
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const int r = lane & 15, g = lane >> 4;
-  if constexpr (!GO) {                        // (the weights are no part of the feature pull)
-#pragma unroll 2
-    for (int idx = tid; idx < kGeoFrag / 4; idx += 512)
-      reinterpret_cast<float4*>(smem)[idx] = reinterpret_cast<const float4*>(frags)[idx];
-    if (tid < 128) reinterpret_cast<float4*>(smem + kGeoFrag)[tid] = reinterpret_cast<const float4*>(wout)[tid];
-  }
-  __syncthreads();
-  // persistent over the sample blocks: the 61 KB of fragments are staged once per workgroup (a launch used to stage them
-  // for every 128 samples, 4800 times per 614k-sample batch, with the first MFMA of a workgroup waiting behind it)
-  const int nblk = (Q + kTM2 - 1) / kTM2;
-  // per-sample inputs of a block: position, neighbour ids, IDW weights.  They are requested one block AHEAD, so a block's
-  // feature gather (which needs the ids) starts at once instead of behind a second dependent memory round trip
-  struct Meta { float x, y, z; int id[8]; float wk[8]; bool on; };
-  auto load_meta = [&](int blk, Meta& m) {
-    const int qq = min(blk * kTM2 + wv * 16 + r, Q - 1);
-    m.x = pts[(size_t)qq * 3 + 0]; m.y = pts[(size_t)qq * 3 + 1]; m.z = pts[(size_t)qq * 3 + 2];
-    m.on = has[qq] != 0;
-    if (geo_feats) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        m.id[k] = (int)max(I[(size_t)qq * 8 + k], 0L);
-        m.wk[k] = wts[(size_t)qq * 8 + k];
-      }
-    }
-  };
-  Meta cur;
-  if ((int)blockIdx.x < nblk) load_meta(blockIdx.x, cur);
-  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-  const int qs = blk * kTM2 + wv * 16 + r;
-  const int q = min(qs, Q - 1);
-  h16x8 chi, clo, hhi, hlo;
-  f32x4 acc[2];
-  const float x = cur.x, y = cur.y, z = cur.z;
-  const bool on = cur.on;
-  Meta nxt = cur;
-  {
-    f32x4 c[2];
-    if (geo_feats) {
-      // IDW interpolation of the neighbours' features (decoder.py:130-173), as in mlp_geo_v3_kernel
-      c[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-      c[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      constexpr int GEO_NB = GLORIE_GEO_NB;
-#pragma unroll
-      for (int k0 = 0; k0 < 8; k0 += GEO_NB) {
-        float4 v[GEO_NB][2];
-#pragma unroll
-        for (int k = 0; k < GEO_NB; ++k) {
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            v[k][t] = *reinterpret_cast<const float4*>(geo_feats + (size_t)cur.id[k0 + k] * 32 + 16 * t + 4 * g);
-        }
-        if (k0 == 0 && blk + (int)gridDim.x < nblk) load_meta(blk + gridDim.x, nxt);   // behind the first gathers
-#pragma unroll
-        for (int k = 0; k < GEO_NB; ++k) {
-          const float wk = cur.wk[k0 + k];
-          const bool use = on && wk != 0.0f;
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            c[t][0] = use ? c[t][0] + wk * v[k][t].x : c[t][0];
-            c[t][1] = use ? c[t][1] + wk * v[k][t].y : c[t][1];
-            c[t][2] = use ? c[t][2] + wk * v[k][t].z : c[t][2];
-            c[t][3] = use ? c[t][3] + wk * v[k][t].w : c[t][3];
-          }
-        }
-      }
-    } else {
-      if (blk + (int)gridDim.x < nblk) load_meta(blk + gridDim.x, nxt);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float4 v = *reinterpret_cast<const float4*>(c_geo + (size_t)q * 32 + 16 * t + 4 * g);
-        c[t][0] = v.x; c[t][1] = v.y; c[t][2] = v.z; c[t][3] = v.w;
-      }
-    }
-    split2(c[0], c[1], chi, clo);
-    if constexpr (GO) {
-      // the interpolated feature's sum stands in for the occupancy
-      if (g == 0 && qs < Q) raw[(size_t)qs * 4 + 3] = (c[0][0] + c[0][1]) + (c[1][2] + c[1][3]);
-      cur = nxt;
-      continue;
-    }
-  }
-  auto act = [&](int li) {   // ReLU(acc + bias) + fc_c bias
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float4 bb = *reinterpret_cast<const float4*>(P.bias + li * 32 + 16 * t + 4 * g);
-      const float4 fb = *reinterpret_cast<const float4*>(P.fcb + li * 32 + 16 * t + 4 * g);
-      acc[t][0] = relu_keep_nan(acc[t][0] + bb.x) + fb.x;
-      acc[t][1] = relu_keep_nan(acc[t][1] + bb.y) + fb.y;
-      acc[t][2] = relu_keep_nan(acc[t][2] + bb.z) + fb.z;
-      acc[t][3] = relu_keep_nan(acc[t][3] + bb.w) + fb.w;
-    }
-  };
-  auto next_layer = [&]() {
-    split2(acc[0], acc[1], hhi, hlo);
-    zero<2>(acc);
-  };
-  auto ch = [&](int c) { return smem + c * 1024; };
-  // embedding blocks (2cc, 2cc + 1) -> chunk `chunk`: evaluated, split, multiplied, forgotten
-  auto embed = [&](int cc, int chunk) {
-    f32x4 e[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int t = 2 * cc + u;
-      const float4 b0 = *reinterpret_cast<const float4*>(P.B + 16 * t + 4 * g);
-      const float4 b1 = *reinterpret_cast<const float4*>(P.B + 96 + 16 * t + 4 * g);
-      const float4 b2 = *reinterpret_cast<const float4*>(P.B + 192 + 16 * t + 4 * g);
-      e[u][0] = sin_rev(fmaf(z, b2.x, fmaf(y, b1.x, x * b0.x)));
-      e[u][1] = sin_rev(fmaf(z, b2.y, fmaf(y, b1.y, x * b0.y)));
-      e[u][2] = sin_rev(fmaf(z, b2.z, fmaf(y, b1.z, x * b0.z)));
-      e[u][3] = sin_rev(fmaf(z, b2.w, fmaf(y, b1.w, x * b0.w)));
-    }
-    h16x8 ehi, elo;
-    split2(e[0], e[1], ehi, elo);
-    mma_g3(acc, ehi, elo, ch(chunk));
-  };
-  // chunks: W0 0-2 | Fc0 3 | W1 4 | Fc1 5 | W2 6 | Fc2 7 | W3e 8-10 | W3h 11 | Fc3 12 | W4 13 | Fc4 14
-  zero<2>(acc);
-  embed(0, 0); embed(1, 1); embed(2, 2);
-  act(0); mma_g3(acc, chi, clo, ch(3));
-  next_layer();
-  mma_g3(acc, hhi, hlo, ch(4));  act(1); mma_g3(acc, chi, clo, ch(5));
-  next_layer();
-  mma_g3(acc, hhi, hlo, ch(6));  act(2); mma_g3(acc, chi, clo, ch(7));
-  next_layer();
-  embed(0, 8); embed(1, 9); embed(2, 10);
-  mma_g3(acc, hhi, hlo, ch(11)); act(3); mma_g3(acc, chi, clo, ch(12));
-  next_layer();
-  mma_g3(acc, hhi, hlo, ch(13)); act(4); mma_g3(acc, chi, clo, ch(14));
-  // output layer 32 -> 1 (16 padded columns) in fp32: lanes with g == 0 get channel 0 of their sample in o[0]
-  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-  {
-    const float* wp = smem + kGeoFrag + (4 * g) * 16 + r;
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr)
-        o = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 16], acc[t][rr], o, 0, 0, 0);
-  }
-  if (g == 0 && qs < Q) {
-    bad = bad | (on && not_finite(o[0]));
-    raw[(size_t)qs * 4 + 3] = on ? o[0] + P.bout[0] : -100.0f;  // Renderer.py:206-207
-  }
-  cur = nxt;
-  }
-  report_range(bad, range_flag);
-}
-
-// per-neighbour F_theta on the fp16 matrix cores with the 3-term split (see mlp_col_v5_kernel).  The 52 input channels of a
-// neighbour are two 32-slot chunks: chunk 0 = the 20 embedding features (lane slot s < 5 <-> feature 4s + g, slots 5..7
-// zero), chunk 1 = the 32 colour-feature channels (slot s <-> channel 16 (s >> 2) + 4 g + (s & 3), the two 16-byte loads of
-// the feature row).  W1 is packed split, as A fragments [chunk][hi|lo][out block][lane][8] (point_ops.pack_decoders), and copied
-// to LDS once per workgroup.
-template <bool GO>
-__global__ __launch_bounds__(512, 4) void mlp_nb_v4_kernel(NbParams P, const float* __restrict__ W1frag,
-                                                           const float* __restrict__ pts,
-                                                           const float* __restrict__ cloud,
-                                                           const float* __restrict__ col_feats,
-                                                           const int64_t* __restrict__ I,
-                                                           const float* __restrict__ wts,
-                                                           const uint8_t* __restrict__ has, int Q,
-                                                           float* __restrict__ c_col, int* __restrict__ range_flag) {
-  bool bad = false;
-  extern __shared__ float smem[];
-  h16x8* W1f = reinterpret_cast<h16x8*>(smem);   // [2 chunks][2 hi|lo][8][64] fragments of 8 halfs = 32 KB
-  float* b1s = smem + 8192;                   // [128]
-  float* wbuf = b1s + 128;                    // [128][8] IDW weights (0 for an absent neighbour)
-  int* ibuf = reinterpret_cast<int*>(wbuf + kTM2 * 8);  // [128][8] neighbour ids (0 for an absent one)
-  float* bs = reinterpret_cast<float*>(ibuf + kTM2 * 8);  // [20][4] B[:, f mod 10] (revolutions per metre)
-  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const int r = lane & 15, g = lane >> 4;
-  const int q0 = blockIdx.x * kTM2;
-  if (tid < 80) {
-    const int f = tid >> 2, d = tid & 3;
-    bs[tid] = d < 3 ? P.B[d * 10 + (f < 10 ? f : f - 10)] : 0.0f;
-  }
-  if constexpr (!GO) {                                        // (the weights are no part of the feature pull)
-    for (int idx = tid; idx < 8192 / 4; idx += 512)           // the split fragments as packed (point_ops.pack_decoders)
-      reinterpret_cast<float4*>(smem)[idx] = reinterpret_cast<const float4*>(W1frag)[idx];
-    if (tid < 128) b1s[tid] = P.b1[tid];
-  }
-  for (int idx = tid; idx < kTM2 * 8; idx += 512) {
-    const int row = idx >> 3;
-    const int q = min(q0 + row, Q - 1);
-    const int ii = (int)I[(size_t)q * 8 + (idx & 7)];
-    wbuf[idx] = (q0 + row < Q && ii >= 0) ? wts[(size_t)q * 8 + (idx & 7)] : 0.0f;
-    ibuf[idx] = ii < 0 ? 0 : ii;
-  }
-  __syncthreads();
-  const int srow = wv * 16 + r;               // this lane's sample row inside the workgroup
-  const int qs = q0 + srow;
-  const int q = min(qs, Q - 1);
-  const float qx = pts[(size_t)q * 3 + 0], qy = pts[(size_t)q * 3 + 1], qz = pts[(size_t)q * 3 + 2];
-  const float* bsl = bs + 4 * g;
-  f32x4 ysum[8];
-  zero<8>(ysum);
-  float sw = 0.0f;
-  const h16x8* wl = W1f + lane;
-#pragma unroll 1
-  for (int k = 0; k < 8; ++k) {
-#ifdef EXP_NB_NO_GATHER
-    const int pt = (q0 + srow) & 0xffff;                    // ablation: consecutive rows instead of the neighbours'
-#else
-    const int pt = ibuf[srow * 8 + k];
-#endif
-    const float w = wbuf[srow * 8 + k];
-    const float4 c0 = *reinterpret_cast<const float4*>(col_feats + (size_t)pt * 32 + 4 * g);
-    const float4 c1 = *reinterpret_cast<const float4*>(col_feats + (size_t)pt * 32 + 16 + 4 * g);
-    const float rx = cloud[(size_t)pt * 3 + 0] - qx, ry = cloud[(size_t)pt * 3 + 1] - qy,
-                rz = cloud[(size_t)pt * 3 + 2] - qz;
-    if constexpr (GO) {
-      // measurement instantiation: the neighbour's feature row and position, weighted - no embedding, no layers
-      ysum[0][0] += w * (c0.x + c1.x + rx); ysum[0][1] += w * (c0.y + c1.y + ry);
-      ysum[0][2] += w * (c0.z + c1.z + rz); ysum[0][3] += w * (c0.w + c1.w);
-      sw += w;
-      continue;
-    }
-    f32x4 acc[8];
-    zero<8>(acc);
-    // chunk 0: embedding features 4s + g (sin for feature < 10), phases in revolutions
-    {
-      float ev[8];
-#pragma unroll
-      for (int sidx = 0; sidx < 5; ++sidx) {
-        const float4 bf = *reinterpret_cast<const float4*>(bsl + 16 * sidx);
-        const float a = fmaf(rz, bf.z, fmaf(ry, bf.y, rx * bf.x));
-#ifdef EXP_NB_NO_SINCOS
-        ev[sidx] = a;
-#else
-        ev[sidx] = (4 * sidx + g >= 10) ? cos_rev(a) : sin_rev(a);
-#endif
-      }
-      ev[5] = ev[6] = ev[7] = 0.0f;
-      h16x8 bhi, blo;
-      split2(f32x4{ev[0], ev[1], ev[2], ev[3]}, f32x4{ev[4], ev[5], ev[6], ev[7]}, bhi, blo);
-#pragma unroll
-      for (int to = 0; to < 8; ++to) {
+  for (int to = 0; to < 8; ++to) {
 #ifdef EXP_NB_NO_LDSW
-        const h16x8 ahi = bhi, alo = blo;                     // ablation: no fragment reads
+    const h16x8 ahi = bhi, alo = blo;                     // ablation: no fragment reads
 #else
-        const h16x8 ahi = wl[to * 64], alo = wl[(8 + to) * 64];
+    const h16x8 ahi = wl[(FRAG0 + to) * 64], alo = wl[(FRAG0 + 8 + to) * 64];
 #endif
 #ifdef EXP_NB_NO_MFMA
-        acc[to][0] += (float)ahi[0] * (float)bhi[to & 7] + (float)alo[1] * (float)blo[to & 7];      // ablation: no matrix work
+    acc[to][FRAG0 / 16] += (float)ahi[0] * (float)bhi[to & 7] + (float)alo[1] * (float)blo[to & 7];      // ablation: no matrix work
 #else
-        acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc[to], 0, 0, 0);
-        acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc[to], 0, 0, 0);
-        acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc[to], 0, 0, 0);
+    acc[to] = mfma_h3(ahi, alo, bhi, blo, acc[to]);
 #endif
-        __builtin_amdgcn_sched_barrier(0);     // keeps the compiler from hoisting all 32 fragment reads (128 registers)
-      }
-    }
-    // chunk 1: the neighbour's colour feature (a full L2 round trip behind the index: issued above, used here)
-    {
-      h16x8 bhi, blo;
-      split2(f32x4{c0.x, c0.y, c0.z, c0.w}, f32x4{c1.x, c1.y, c1.z, c1.w}, bhi, blo);
-#pragma unroll
-      for (int to = 0; to < 8; ++to) {
-#ifdef EXP_NB_NO_LDSW
-        const h16x8 ahi = bhi, alo = blo;
-#else
-        const h16x8 ahi = wl[(16 + to) * 64], alo = wl[(24 + to) * 64];
-#endif
-#ifdef EXP_NB_NO_MFMA
-        acc[to][1] += (float)ahi[0] * (float)bhi[to & 7] + (float)alo[1] * (float)blo[to & 7];
-#else
-        acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc[to], 0, 0, 0);
-        acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc[to], 0, 0, 0);
-        acc[to] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc[to], 0, 0, 0);
-#endif
-        __builtin_amdgcn_sched_barrier(0);     // keeps the compiler from hoisting all 32 fragment reads (128 registers)
-      }
-    }
-    sw += w;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const float4 bb = *reinterpret_cast<const float4*>(b1s + 16 * t + 4 * g);
-      ysum[t][0] += w * softplus100_fast(acc[t][0] + bb.x);
-      ysum[t][1] += w * softplus100_fast(acc[t][1] + bb.y);
-      ysum[t][2] += w * softplus100_fast(acc[t][2] + bb.z);
-      ysum[t][3] += w * softplus100_fast(acc[t][3] + bb.w);
-    }
+    __builtin_amdgcn_sched_barrier(0);     // keeps the compiler from hoisting all 32 fragment reads (128 registers)
   }
-  // second layer 128 -> 32 in fp32 as in mlp_nb_v3_kernel (A = W2 straight from global / L2)
-  f32x4 o[2];
-  zero<2>(o);
-  {
-    const float* wp = P.W2 + (4 * g) * 32 + r;
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        o[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 32], ysum[t][rr], o[0], 0, 0, 0);
-        o[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[(16 * t + rr) * 32 + 16], ysum[t][rr], o[1], 0, 0, 0);
-      }
-  }
-  if (qs < Q) {
-    const bool h = has[qs] != 0;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float4 b2 = *reinterpret_cast<const float4*>(P.b2 + 16 * t + 4 * g);
-      float4 v;
-      v.x = h ? o[t][0] + b2.x * sw : 0.0f;
-      v.y = h ? o[t][1] + b2.y * sw : 0.0f;
-      v.z = h ? o[t][2] + b2.z * sw : 0.0f;
-      v.w = h ? o[t][3] + b2.w * sw : 0.0f;
-      bad = bad | not_finite(v.x + v.y + v.z + v.w);
-      *reinterpret_cast<float4*>(c_col + (size_t)qs * 32 + 16 * t + 4 * g) = v;
-    }
-  }
-  report_range(bad, range_flag);
 }
 
-// Round 3, measured and not kept for the per-neighbour kernel (614,400 samples, v4 = 394 us): two column blocks per wave in
+// The 52 input channels of a neighbour are two 32-slot chunks: chunk 0 = the 20 embedding features (lane slot s < 5 <->
+// feature 4s + g, slots 5..7 zero), chunk 1 = the 32 colour-feature channels (slot s <-> channel 16 (s >> 2) + 4 g + (s & 3),
+// the two 16-byte loads of the feature row).  W1 is packed split, as A fragments [chunk][hi|lo][out block][lane][8]
+// (point_ops.pack_decoders), and copied to LDS once per workgroup.  GO: see mlp_geo_v4_kernel.
+//
+// Round 3, measured and not kept (614,400 samples, this kernel = 394 us): two column blocks per wave in
 // lockstep 415-463 us; two accumulator sets with the MFMAs of neighbour k+1 issued between the softplus instructions of
 // neighbour k (software pipeline inside the wave) 495 us at 2 waves per SIMD, 624 us at 3 (spills) - four resident waves per
 // SIMD alternating their phases already overlap the matrix pipe with the vector ALU better than one wave can by itself;
@@ -1179,26 +942,91 @@ __global__ __launch_bounds__(512, 4) void mlp_nb_v4_kernel(NbParams P, const flo
 // workgroups; every fragment read feeds six MFMAs; bit-identical) - and a 640x480 frame takes 5.42-5.51 ms with it against
 // 5.42-5.56 ms without, the single-batch 1/8 share 0.894-0.902 against 0.891-0.918 ms (interleaved builds, same box): halving
 // the fragment reads buys exactly what the fourth wave per SIMD was worth.  Not kept either.
+template <bool GO>
+__global__ __launch_bounds__(512, 4) void mlp_nb_v4_kernel(NbParams P, const float* __restrict__ W1frag,
+                                                           const float* __restrict__ pts,
+                                                           const float* __restrict__ cloud,
+                                                           const float* __restrict__ col_feats,
+                                                           const int64_t* __restrict__ I,
+                                                           const float* __restrict__ wts,
+                                                           const uint8_t* __restrict__ has, int Q,
+                                                           float* __restrict__ c_col, int* __restrict__ range_flag) {
+  extern __shared__ float smem[];
+  const NbLds s = nb_lds(smem, kNbFrag);
+  const int tid = threadIdx.x;
+  const int q0 = blockIdx.x * kTM2;
+  if constexpr (!GO) {                                        // (the weights are no part of the feature pull)
+    for (int idx = tid; idx < kNbFrag / 4; idx += 512)        // the split fragments as packed
+      reinterpret_cast<float4*>(smem)[idx] = reinterpret_cast<const float4*>(W1frag)[idx];
+    if (tid < 128) s.b1s[tid] = P.b1[tid];
+  }
+  nb_stage_meta(s, P.B, I, wts, q0, Q);
+  __syncthreads();
+  const Lane L = lane_of(q0, Q);
+  const int g = L.g;
+  const int srow = L.wv * 16 + L.r;           // this lane's sample row inside the workgroup
+  const float qx = pts[(size_t)L.q * 3 + 0], qy = pts[(size_t)L.q * 3 + 1], qz = pts[(size_t)L.q * 3 + 2];
+  const float* bsl = s.bs + 4 * g;
+  f32x4 ysum[8];
+  zero<8>(ysum);
+  float sw = 0.0f;
+  const h16x8* wl = reinterpret_cast<const h16x8*>(smem) + L.lane;
+#pragma unroll 1
+  for (int k = 0; k < 8; ++k) {
+    const NbRow n = nb_row(s, srow, k, cloud, col_feats, g, qx, qy, qz, L.qs);
+    if constexpr (GO) {
+      // measurement instantiation: the neighbour's feature row and position, weighted - no embedding, no layers
+      ysum[0][0] += n.w * (n.c0.x + n.c1.x + n.rx); ysum[0][1] += n.w * (n.c0.y + n.c1.y + n.ry);
+      ysum[0][2] += n.w * (n.c0.z + n.c1.z + n.rz); ysum[0][3] += n.w * (n.c0.w + n.c1.w);
+      sw += n.w;
+      continue;
+    }
+    f32x4 acc[8];
+    zero<8>(acc);
+    h16x8 bhi, blo;
+    // chunk 0: the embedding features
+    split2(f32x4{nb_embed(n, bsl, 0, g), nb_embed(n, bsl, 1, g), nb_embed(n, bsl, 2, g), nb_embed(n, bsl, 3, g)},
+           f32x4{nb_embed(n, bsl, 4, g), 0.0f, 0.0f, 0.0f}, bhi, blo);
+    nb_chunk_h3<0>(acc, bhi, blo, wl);
+    // chunk 1: the neighbour's colour feature (a full L2 round trip behind the index: issued above, used here)
+    split2(as_f32x4(n.c0), as_f32x4(n.c1), bhi, blo);
+    nb_chunk_h3<16>(acc, bhi, blo, wl);
+    sw += n.w;
+    nb_accumulate(ysum, acc, n.w, s.b1s, g);
+  }
+  report_range(nb_finish(ysum, sw, P, L, Q, has, c_col), range_flag);
+}
 }  // namespace glorie
 
 using namespace glorie;
 
-// offsets (in floats) of every section inside the packed parameter buffer; the layout is
-// produced by glorie_slam_amd.point_ops.pack_decoders and mirrored here.
+// ---- the packed parameter buffer: its sections in order, sizes in floats.  point_ops.pack_decoders writes them in this
+// order; the size the library reports and every pointer handed to a kernel come from this one list ----
 namespace {
-struct Cursor {
-  const float* p;
-  const float* take(size_t n) { const float* r = p; p += n; return r; }
+enum PackSection {
+  kSecGeoB, kSecGeoBias, kSecGeoFcb, kSecGeoBout,                              // GeoParams
+  kSecNbB, kSecNbW1, kSecNbB1, kSecNbW2, kSecNbB2,                             // NbParams
+  kSecColBp, kSecColBv, kSecColWout, kSecColBias, kSecColFcb, kSecColBout,     // ColParams
+  kSecColChunks,  // colour K-rows, 27 chunks of [32][128], columns permuted (mlp_col_v3_kernel)
+  kSecGeoImage,   // geometry K-rows as the LDS image of mlp_geo_v3_kernel; its trailing output layer serves mlp_geo_v4 too
+  kSecColFrags,   // colour chunks as split A fragments (mlp_col_v5_kernel)
+  kSecNbFrags,    // W1 as split A fragments (mlp_nb_v4_kernel)
+  kSecGeoFrags,   // geometry K-rows as split A fragments (mlp_geo_v4_kernel)
+  kPackSections
 };
+constexpr size_t kPackFloats[kPackSections] = {
+    3 * 96, 5 * 32, 5 * 32, 4,
+    3 * 10 + 2 /* pad to 16 bytes */, 52 * 128, 128, 128 * 32, 32,
+    3 * 20, 3 * 20, 128 * 16, 5 * 128, 5 * 128, 4,
+    (size_t)kColChunks * 32 * 128, kGeoImage, (size_t)kColChunks * kChunkFloats16, kNbFrag, kGeoFrag};
+constexpr size_t pack_offset(int section) {
+  size_t o = 0;
+  for (int i = 0; i < section; ++i) o += kPackFloats[i];
+  return o;
+}
 }  // namespace
 
-extern "C" size_t glorie_decoder_pack_floats(void) {
-  size_t geo = 3 * 96 + 96 * 32 + 32 * 32 * 2 + 96 * 32 + 32 * 32 * 2 + 32 * 16 + 5 * 32 * 32 + 5 * 32 * 2 + 4;
-  size_t nb = 3 * 10 + 2 + 52 * 128 + 128 + 128 * 32 + 32;
-  size_t col = 3 * 20 * 2 + 80 * 128 + 128 * 128 * 2 + 80 * 128 + 128 * 128 * 2 + 128 * 16 + 5 * 32 * 128 +
-               5 * 128 * 2 + 4;
-  return geo + nb + col + (size_t)27 * 32 * 128 + (size_t)(480 * 32 + 32 * 16) + (size_t)27 * kChunkFloats16 + (size_t)8192 + (size_t)kGeoFrag;
-}
+extern "C" size_t glorie_decoder_pack_floats(void) { return pack_offset(kPackSections); }
 
 extern "C" int glorie_render_mlp(const float* packed, const float* pts, const float* views,
                                  const float* cloud_pos, const float* col_feats,
@@ -1214,100 +1042,49 @@ extern "C" int glorie_render_mlp(const float* packed, const float* pts, const fl
   if (!c_geo && !(geo_feats && I && weights)) return GLORIE_EINVAL;   // interpolated feature, or what it takes
   if (stage_color && (!views || !cloud_pos || !col_feats || !I || !weights || !c_col_scratch))
     return GLORIE_EINVAL;
+  if (gather_only && (force_f32 || !(geo_feats && I && weights))) return GLORIE_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  Cursor c{packed};
-  GeoParams g;
-  g.B = c.take(3 * 96); g.W0 = c.take(96 * 32); g.W1 = c.take(32 * 32); g.W2 = c.take(32 * 32);
-  g.W3e = c.take(96 * 32); g.W3h = c.take(32 * 32); g.W4 = c.take(32 * 32); g.Wout = c.take(32 * 16);
-  g.Fc = c.take(5 * 32 * 32); g.bias = c.take(5 * 32); g.fcb = c.take(5 * 32);
-  g.bout = c.take(4);
-  NbParams n;
-  n.B = c.take(3 * 10); c.take(2); n.W1 = c.take(52 * 128); n.b1 = c.take(128); n.W2 = c.take(128 * 32);
-  n.b2 = c.take(32);
-  ColParams k;
-  k.Bp = c.take(3 * 20); k.Bv = c.take(3 * 20); k.W0 = c.take(80 * 128); k.W1 = c.take(128 * 128);
-  k.W2 = c.take(128 * 128); k.W3e = c.take(80 * 128); k.W3h = c.take(128 * 128); k.W4 = c.take(128 * 128);
-  k.Wout = c.take(128 * 16); k.Fc = c.take(5 * 32 * 128); k.bias = c.take(5 * 128); k.fcb = c.take(5 * 128);
-  k.bout = c.take(4);
-  const float* col_chunks = c.take((size_t)27 * 32 * 128);
-  const float* geo_image = c.take((size_t)kGeoImage);
-  const float* col_chunks16 = c.take((size_t)27 * kChunkFloats16);
-  const float* nb_frags = c.take((size_t)8192);
-  const float* geo_frags = c.take((size_t)kGeoFrag);
-  const int blocks2 = (Q + kTM2 - 1) / kTM2;
-  const size_t geo_lds = sizeof(float) * kGeoImage;
-  static PerDeviceOnce geo_attr;
-  if (geo_attr.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_geo_v3_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo_lds);
-  }
+  auto at = [&](PackSection s) { return packed + pack_offset(s); };
+  const GeoParams g{at(kSecGeoB), at(kSecGeoBias), at(kSecGeoFcb), at(kSecGeoBout)};
+  const NbParams n{at(kSecNbB), at(kSecNbW1), at(kSecNbB1), at(kSecNbW2), at(kSecNbB2)};
+  const ColParams k{at(kSecColBp), at(kSecColBv), at(kSecColWout), at(kSecColBias), at(kSecColFcb), at(kSecColBout)};
+  const float* geo_image = at(kSecGeoImage);
+  // fp16 matrix cores with the 3-term split (fp32 accuracy) unless the caller or GLORIE_MLP_F32=1 asks for the fp32 MFMA
+  // kernels; read at every call (bench.py toggles it between launches)
   const char* f32env = getenv("GLORIE_MLP_F32");
-  const bool geo_f32 = force_f32 || (f32env && f32env[0] == '1');
-  const size_t geo4_lds = sizeof(float) * (kGeoFrag + 32 * 16);
-  static PerDeviceOnce geo4_attr;
-  if (geo4_attr.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_geo_v4_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo4_lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_geo_v4_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)geo4_lds);
-  }
+  const bool precise = force_f32 || (f32env && f32env[0] == '1');
+  const dim3 blocks((Q + kTM2 - 1) / kTM2), threads(512);
+  const dim3 geo4_blocks(blocks.x < 512 ? blocks.x : 512);            // persistent over the sample blocks
+  constexpr size_t geo_lds = sizeof(float) * kGeoImage, geo4_lds = sizeof(float) * (kGeoFrag + kGeoOut);
+  constexpr size_t nb_lds3 = nb_lds_bytes(kNbW1Lds), nb_lds4 = nb_lds_bytes(kNbFrag);
+  constexpr size_t col_lds = sizeof(float) * 2 * kChunkFloats3, col16_lds = sizeof(float) * 2 * kChunkFloats16;
+  // a feature source the kernels ignore is not passed on: c_geo wins over geo_feats (except in the gather measurement)
+  const float* feats = (c_geo && !gather_only) ? nullptr : geo_feats;
   if (gather_only) {
-    if (force_f32 || !(geo_feats && I && weights)) return GLORIE_EINVAL;
-    hipLaunchKernelGGL(mlp_geo_v4_kernel<true>, dim3(blocks2 < 512 ? blocks2 : 512), dim3(512), geo4_lds, st, g, geo_frags,
-                       geo_image + kGeoRows * 32, pts, c_geo, geo_feats, I, weights, has, Q, raw, range_flag);
-    if (stage_color) {
-      const size_t nb4_lds = sizeof(float) * (8192 + 128 + kTM2 * 8 + 80) + sizeof(int) * kTM2 * 8;
-      static PerDeviceOnce attr_go;
-      if (attr_go.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_nb_v4_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb4_lds);
-      }
-      hipLaunchKernelGGL(mlp_nb_v4_kernel<true>, dim3(blocks2), dim3(512), nb4_lds, st, n, nb_frags, pts, cloud_pos, col_feats,
-                         I, weights, has, Q, c_col_scratch, range_flag);
-    }
+    GLORIE_TRY(launch_lds<mlp_geo_v4_kernel<true>>(geo4_blocks, threads, geo4_lds, st, g, at(kSecGeoFrags), geo_image + kGeoRows * 32,
+                                                   pts, c_geo, feats, I, weights, has, Q, raw, range_flag));
+    if (stage_color)
+      GLORIE_TRY(launch_lds<mlp_nb_v4_kernel<true>>(blocks, threads, nb_lds4, st, n, at(kSecNbFrags), pts, cloud_pos, col_feats, I,
+                                                    weights, has, Q, c_col_scratch, range_flag));
     return check_launch();
   }
-  if (geo_f32)
-    hipLaunchKernelGGL(mlp_geo_v3_kernel, dim3(blocks2), dim3(512), geo_lds, st, g, geo_image, pts, c_geo,
-                       c_geo ? nullptr : geo_feats, I, weights, has, Q, raw);
+  if (precise)
+    GLORIE_TRY(launch_lds<mlp_geo_v3_kernel>(blocks, threads, geo_lds, st, g, geo_image, pts, c_geo, feats, I, weights, has, Q,
+                                             raw));
   else
-    hipLaunchKernelGGL(mlp_geo_v4_kernel<false>, dim3(blocks2 < 512 ? blocks2 : 512), dim3(512), geo4_lds, st, g, geo_frags,
-                       geo_image + kGeoRows * 32, pts, c_geo, c_geo ? nullptr : geo_feats, I, weights, has, Q, raw,
-                       range_flag);
-  if (stage_color) {
-    const size_t nb_lds = sizeof(float) * (52 * kLdw3 + 128 + kTM2 * 8 + 80) + sizeof(int) * kTM2 * 8;
-    const size_t col_lds = sizeof(float) * 2 * kChunkFloats3;
-    static PerDeviceOnce attr;
-    if (attr.first()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_nb_v3_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb_lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_col_v3_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)col_lds);
-    }
-    // per-neighbour and colour decoders: fp16 matrix cores with the 3-term split (fp32 accuracy); GLORIE_MLP_F32=1 keeps
-    // the fp32 MFMA kernels
-    const char* f32 = force_f32 ? "1" : getenv("GLORIE_MLP_F32");
-    const size_t nb4_lds = sizeof(float) * (8192 + 128 + kTM2 * 8 + 80) + sizeof(int) * kTM2 * 8;
-    static PerDeviceOnce attr4;
-    if (attr4.first()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_nb_v4_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb4_lds);
-    }
-    // colour decoder: 32 samples per wave, 4 waves per workgroup (measured per 614k-sample batch against 16 samples per wave
-    // and against 8-wave workgroups: 427 vs 495 / 485 us; the other two forms were removed in round 4)
-    if (f32 && f32[0] == '1')
-      hipLaunchKernelGGL(mlp_nb_v3_kernel, dim3(blocks2), dim3(512), nb_lds, st, n, pts, cloud_pos, col_feats,
-                         I, weights, has, Q, c_col_scratch);
-    else
-      hipLaunchKernelGGL(mlp_nb_v4_kernel<false>, dim3(blocks2), dim3(512), nb4_lds, st, n, nb_frags, pts, cloud_pos, col_feats,
-                         I, weights, has, Q, c_col_scratch, range_flag);
-    const size_t col16_lds = sizeof(float) * 2 * kChunkFloats16;
-    if (f32 && f32[0] == '1')
-      hipLaunchKernelGGL(mlp_col_v3_kernel, dim3(blocks2), dim3(512), col_lds, st, k, col_chunks, pts, views,
-                         c_col_scratch, Q, raw);
-    else
-      hipLaunchKernelGGL((mlp_col_v5_kernel<2, 4>), dim3((Q + 127) / 128), dim3(256), col16_lds, st, k, col_chunks16, pts,
-                         views, c_col_scratch, Q, raw, range_flag);
+    GLORIE_TRY(launch_lds<mlp_geo_v4_kernel<false>>(geo4_blocks, threads, geo4_lds, st, g, at(kSecGeoFrags),
+                                                    geo_image + kGeoRows * 32, pts, c_geo, feats, I, weights, has, Q, raw,
+                                                    range_flag));
+  if (stage_color && precise) {
+    GLORIE_TRY(launch_lds<mlp_nb_v3_kernel>(blocks, threads, nb_lds3, st, n, pts, cloud_pos, col_feats, I, weights, has, Q,
+                                            c_col_scratch));
+    GLORIE_TRY(launch_lds<mlp_col_v3_kernel>(blocks, threads, col_lds, st, k, at(kSecColChunks), pts, views, c_col_scratch, Q, raw));
+  } else if (stage_color) {
+    GLORIE_TRY(launch_lds<mlp_nb_v4_kernel<false>>(blocks, threads, nb_lds4, st, n, at(kSecNbFrags), pts, cloud_pos, col_feats, I,
+                                                   weights, has, Q, c_col_scratch, range_flag));
+    // 32 samples per wave, 4 waves per workgroup
+    GLORIE_TRY((launch_lds<mlp_col_v5_kernel<2, 4>>(dim3((Q + 127) / 128), dim3(256), col16_lds, st, k, at(kSecColFrags), pts, views,
+                                                    c_col_scratch, Q, raw, range_flag)));
   }
   return check_launch();
 }

@@ -259,102 +259,70 @@ def _pad_cols(m, cols):
     return out
 
 
+def _layer_rows(m, emb):
+    """K-rows of a decoder's 11-matrix layer sequence, 32 rows per chunk:
+    W0(emb->96) Fc0 | W1 Fc1 | W2 Fc2 | W3e(emb->96) W3h Fc3 | W4 Fc4  (layer 3 is the skip: rows 0..emb-1 of its
+    weight meet the embedding, the rest the hidden state)"""
+    w = [_t(l.weight) for l in m.pts_linears]
+    fc = [_t(l.weight) for l in m.fc_c]
+    return torch.cat([_pad_rows(w[0], 96), fc[0], w[1], fc[1], w[2], fc[2], _pad_rows(w[3][:emb], 96), w[3][emb:], fc[3],
+                      w[4], fc[4]], 0).detach().float()
+
+
+def _split_frags(rows, nout):
+    """[chunks * 32, 16 * nout] K-rows -> fp16 MFMA A fragments of the 3-term split, as raw bits in float32:
+    [chunk][hi|lo][out block to][lane = 16 g + i][slot s] halfs, chunk row 16 (s >> 2) + 4 g + (s & 3), output 16 to + i;
+    hi = fp16(w), lo = fp16(w - hi)"""
+    t6 = rows.reshape(-1, 2, 4, 4, nout, 16).permute(0, 4, 2, 5, 1, 3)        # [chunk][to][g][i][s >> 2][s & 3]
+    hi = t6.half()
+    lo = (t6 - hi.float()).half()
+    return torch.stack([hi, lo], 1).reshape(-1).contiguous().view(torch.float32)
+
+
 def pack_decoders(decoders):
-    """Flatten a POINT module into the parameter buffer of glorie_render_mlp (layout mirrored in
-    csrc/mlp.hip: GeoParams | NbParams | ColParams)."""
+    """Flatten a POINT module into the parameter buffer of glorie_render_mlp (sections in the order of kPackFloats in
+    csrc/mlp.hip: what the kernels read through GeoParams | NbParams | ColParams, then the layer weights in the forms the
+    kernels stage)."""
     g, c = decoders.geo_decoder, decoders.color_decoder
+    n = c.mlp_col_neighbor
     dev = next(decoders.parameters()).device
     f = lambda t: t.detach().float().reshape(-1).to(dev)
-    parts = []
-    # geometry
-    parts.append(f(_pad_cols(g.embedder._B.detach().float().to(dev), 96)))
-    parts.append(f(_pad_rows(_t(g.pts_linears[0].weight), 96)))
-    parts.append(f(_t(g.pts_linears[1].weight)))
-    parts.append(f(_t(g.pts_linears[2].weight)))
-    w3 = _t(g.pts_linears[3].weight)                       # [125, 32]: rows 0..92 embedding, 93..124 hidden
-    parts.append(f(_pad_rows(w3[:93], 96)))
-    parts.append(f(w3[93:]))
-    parts.append(f(_t(g.pts_linears[4].weight)))
-    parts.append(f(_pad_cols(_t(g.output_linear.weight), 16)))
-    parts.append(torch.cat([f(_t(l.weight)) for l in g.fc_c]))
-    parts.append(torch.cat([f(l.bias) for l in g.pts_linears]))
-    parts.append(torch.cat([f(l.bias) for l in g.fc_c]))
-    parts.append(torch.cat([f(g.output_linear.bias), torch.zeros(3, device=dev)]))
-    # per-neighbour F_theta (of the colour decoder)
-    n = c.mlp_col_neighbor
-    parts.append(f(c.embedder_rel_pos._B))
-    parts.append(torch.zeros(2, device=dev))
-    parts.append(f(_t(n.linear1.weight)))
-    parts.append(f(n.linear1.bias))
-    parts.append(f(_t(n.linear2.weight)))
-    parts.append(f(n.linear2.bias))
-    # colour
-    parts.append(f(c.embedder._B.to(dev)))
-    parts.append(f(c.embedder_view_direction._B.to(dev)))
-    parts.append(f(_t(c.pts_linears[0].weight)))
-    parts.append(f(_t(c.pts_linears[1].weight)))
-    parts.append(f(_t(c.pts_linears[2].weight)))
-    w3 = _t(c.pts_linears[3].weight)                       # [208, 128]: rows 0..79 embedding
-    parts.append(f(w3[:80]))
-    parts.append(f(w3[80:]))
-    parts.append(f(_t(c.pts_linears[4].weight)))
-    parts.append(f(_pad_cols(_t(c.output_linear.weight), 16)))
-    parts.append(torch.cat([f(_t(l.weight)) for l in c.fc_c]))
-    parts.append(torch.cat([f(l.bias) for l in c.pts_linears]))
-    parts.append(torch.cat([f(l.bias) for l in c.fc_c]))
-    parts.append(torch.cat([f(c.output_linear.bias), torch.zeros(1, device=dev)]))
-    # colour weights once more, in the 32-row chunk order the colour kernel streams through LDS:
-    # W0(80->96) Fc0 | W1 Fc1 | W2 Fc2 | W3e(80->96) W3h Fc3 | W4 Fc4   = 27 chunks of [32,128];
-    # inside a row, output column 16*to + r sits at (to >> 2) * 64 + 4*r + (to & 3) (two 16-byte LDS
-    # reads per lane fetch the eight MFMA A operands of a k-step)
-    w3 = _t(c.pts_linears[3].weight)
-    fc = [_t(l.weight) for l in c.fc_c]
-    seq = [_pad_rows(_t(c.pts_linears[0].weight), 96), fc[0], _t(c.pts_linears[1].weight), fc[1],
-           _t(c.pts_linears[2].weight), fc[2], _pad_rows(w3[:80], 96), w3[80:], fc[3],
-           _t(c.pts_linears[4].weight), fc[4]]
-    chunks = torch.cat([m.to(dev) for m in seq], 0)
-    assert chunks.shape == (27 * 32, 128), chunks.shape
-    chunks16 = chunks.detach().float()
-    chunks = chunks.reshape(-1, 2, 4, 16).permute(0, 1, 3, 2).reshape(-1, 128)
-    parts.append(f(chunks))
-    # geometry weights once more, as the LDS image of the geometry kernel: 480 K-rows
-    # W0(93->96) Fc0 | W1 Fc1 | W2 Fc2 | W3e(93->96) W3h Fc3 | W4 Fc4, output 16*to + r of a row at 2*r + to,
-    # followed by the output layer [32,16] in natural order
-    w3 = _t(g.pts_linears[3].weight)
-    fc = [_t(l.weight) for l in g.fc_c]
-    seq = [_pad_rows(_t(g.pts_linears[0].weight), 96), fc[0], _t(g.pts_linears[1].weight), fc[1],
-           _t(g.pts_linears[2].weight), fc[2], _pad_rows(w3[:93], 96), w3[93:], fc[3],
-           _t(g.pts_linears[4].weight), fc[4]]
-    rows = torch.cat([m.to(dev) for m in seq], 0)
-    assert rows.shape == (480, 32), rows.shape
-    geo_rows16 = rows.detach().float()
-    parts.append(f(rows.reshape(480, 2, 16).permute(0, 2, 1)))
-    parts.append(f(_pad_cols(_t(g.output_linear.weight), 16)))
-    # the colour chunks a third time, as fp16 MFMA A fragments of the 3-term split (mlp_col_v4_kernel):
-    # [chunk][hi|lo][out block to][lane = 16 g + i][slot s] halfs, chunk row 16 (s >> 2) + 4 g + (s & 3), output 16 to + i;
-    # hi = fp16(w), lo = fp16(w - hi); carried as raw bits in the float buffer (4096 floats per chunk)
-    t6 = chunks16.reshape(27, 2, 4, 4, 8, 16).permute(0, 4, 2, 5, 1, 3)       # [chunk][to][g][i][s >> 2][s & 3]
-    hi = t6.half()
-    lo = (t6 - hi.float()).half()
-    frag = torch.stack([hi, lo], 1).reshape(27, -1).contiguous()              # [chunk][2 * 8 * 64 * 8]
-    parts.append(frag.view(torch.float32).reshape(-1))
-    # per-neighbour W1 [52, 128] the same way (mlp_nb_v4_kernel): chunk 0 = the 20 embedding rows (slot s < 5 <-> row 4 s + g,
-    # slots 5..7 zero), chunk 1 = the 32 colour-feature rows (slot s <-> row 20 + 16 (s >> 2) + 4 g + (s & 3))
-    w1 = _t(n.linear1.weight).detach().float().to(dev)                        # [52, 128]
+    geo_rows, col_rows = _layer_rows(g, 93).to(dev), _layer_rows(c, 80).to(dev)
+    assert geo_rows.shape == (480, 32) and col_rows.shape == (27 * 32, 128), (geo_rows.shape, col_rows.shape)
+    # per-neighbour W1 [52, 128] as two 32-row chunks: chunk 0 = the 20 embedding rows (slot s < 5 <-> row 4 s + g, slots
+    # 5..7 zero), chunk 1 = the 32 colour-feature rows in their order
+    w1 = _t(n.linear1.weight).detach().float().to(dev)
     c0 = torch.zeros(8, 4, 128, device=dev)                                   # [s][g][out]
     c0[:5] = w1[:20].reshape(5, 4, 128)
-    c1 = w1[20:52].reshape(2, 4, 4, 128).permute(0, 2, 1, 3).reshape(8, 4, 128)   # [sh][g][sl] -> [s = 4 sh + sl][g]
-    both = torch.stack([c0, c1], 0).reshape(2, 8, 4, 8, 16).permute(0, 3, 2, 4, 1)  # [chunk][to][g][i][s]
-    hi = both.half()
-    lo = (both - hi.float()).half()
-    frag = torch.stack([hi, lo], 1).reshape(-1).contiguous()                  # [chunk][hi|lo][to][g][i][s]
-    parts.append(frag.view(torch.float32).reshape(-1))
-    # ... and the geometry K-rows (mlp_geo_v4_kernel): 15 chunks, 2 output blocks, 1024 floats per chunk
-    t6 = geo_rows16.reshape(15, 2, 4, 4, 2, 16).permute(0, 4, 2, 5, 1, 3)     # [chunk][to][g][i][s >> 2][s & 3]
-    hi = t6.half()
-    lo = (t6 - hi.float()).half()
-    frag = torch.stack([hi, lo], 1).reshape(15, -1).contiguous()              # [chunk][2 * 2 * 64 * 8]
-    parts.append(frag.view(torch.float32).reshape(-1))
+    nb_rows = torch.cat([c0.reshape(2, 4, 4, 128).permute(0, 2, 1, 3).reshape(32, 128), w1[20:52]], 0)
+    parts = [
+        # geometry: Fourier matrix (93 -> 96 columns), pts_linears / fc_c biases, output bias
+        f(_pad_cols(g.embedder._B.detach().float().to(dev), 96)),
+        torch.cat([f(l.bias) for l in g.pts_linears]),
+        torch.cat([f(l.bias) for l in g.fc_c]),
+        torch.cat([f(g.output_linear.bias), torch.zeros(3, device=dev)]),
+        # per-neighbour F_theta (of the colour decoder)
+        f(c.embedder_rel_pos._B), torch.zeros(2, device=dev),
+        f(w1), f(n.linear1.bias), f(_t(n.linear2.weight)), f(n.linear2.bias),
+        # colour: Fourier matrices, output layer (3 -> 16 columns), biases
+        f(c.embedder._B.to(dev)), f(c.embedder_view_direction._B.to(dev)),
+        f(_pad_cols(_t(c.output_linear.weight), 16)),
+        torch.cat([f(l.bias) for l in c.pts_linears]),
+        torch.cat([f(l.bias) for l in c.fc_c]),
+        torch.cat([f(c.output_linear.bias), torch.zeros(1, device=dev)]),
+        # colour K-rows in the 32-row chunks mlp_col_v3_kernel streams through LDS: inside a row, output column 16*to + r
+        # sits at (to >> 2) * 64 + 4*r + (to & 3) (two 16-byte LDS reads per lane fetch the eight MFMA A operands of a k-step)
+        f(col_rows.reshape(-1, 2, 4, 16).permute(0, 1, 3, 2)),
+        # geometry K-rows as the LDS image of mlp_geo_v3_kernel: output 16*to + r of a row at 2*r + to, followed by the output
+        # layer [32,16] in natural order (read by mlp_geo_v4_kernel too)
+        f(geo_rows.reshape(480, 2, 16).permute(0, 2, 1)),
+        f(_pad_cols(_t(g.output_linear.weight), 16)),
+        # the same K-rows as split A fragments: mlp_col_v5_kernel (4096 floats per chunk), mlp_nb_v4_kernel, mlp_geo_v4_kernel
+        # (1024 floats per chunk)
+        _split_frags(col_rows, 8),
+        _split_frags(nb_rows, 8),
+        _split_frags(geo_rows, 2),
+    ]
     packed = torch.cat(parts).contiguous()
     expect = int(L.load().glorie_decoder_pack_floats())
     if packed.numel() != expect:

@@ -607,8 +607,10 @@ int glorie_idw_gather2(const float* D, const int64_t* I, const int* nn, const fl
  *   reference: src/modules/conv_onet/models/decoder.py:175-225 (MLP_geometry.forward),
  *   :340-389 + :228-243 (per-neighbour F_theta + IDW sum), :391-433 (MLP_color.forward),
  *   :460-501 (POINT.forward), src/utils/Renderer.py:206-207 (occupancy -100 without neighbours)
- * packed: glorie_decoder_pack_floats() floats, layout in csrc/mlp.hip (built by
- * glorie_slam_amd.point_ops.pack_decoders from the state dict).  pts/views [Q,3]; cloud_pos
+ * packed: glorie_decoder_pack_floats() floats, the sections of kPackFloats in csrc/mlp.hip in that order: what the kernels
+ * read through pointers (Fourier matrices, biases, the per-neighbour layers, the colour output layer), then the layer
+ * weights in the forms the kernels stage (LDS images for the fp32 MFMA kernels, hi/lo fp16 A fragments for the split
+ * ones); built by glorie_slam_amd.point_ops.pack_decoders from the state dict.  pts/views [Q,3]; cloud_pos
  * [Np,3]; col_feats [Np,32]; c_geo [Q,32] + weights [Q,8] + has [Q] from glorie_idw_gather;
  * I [Q,8] from glorie_knn_query; c_col_scratch [Q,32]; raw [Q,4] = (r,g,b,occ), rgb written
  * only when (stage_flags & 1) (caller zero-fills otherwise).

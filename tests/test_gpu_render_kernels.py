@@ -234,6 +234,31 @@ def test_decoders_match_float64(gpu, name, variant, stage, precise):
     rt.finish()
 
 
+@pytest.mark.parametrize("name", ["1x1", "129x1", "65665x1"])
+def test_gather_phase_only_is_the_interpolated_feature(gpu, name):
+    """stage_flags & 4 (mlp_geo_v4<GO>, what bench.py times as the feature pull): the kernel's own interpolation with the
+    network dropped - column 3 is (f0 + f1) + (f18 + f19) of the interpolated geometry feature, by the IDW family's rule;
+    129 samples give the second workgroup one live sample, 65665 the grid stride and the ragged tail"""
+    from glorie_slam_amd import point_ops
+    c, _, _, cgeo64 = _references(name, "seed43")
+    t, packed = _on_device(name, "seed43", gpu), _packed("seed43", gpu)
+    run = lambda: point_ops.render_mlp(packed, t["pts"], t["views"], t["cloud"], t["col"], None, t["I"], t["w"], t["has"],
+                                       stage="geometry", geo_feats=t["geo"], gather_phase_only=True)
+    raw, again = run(), run()
+    torch.cuda.synchronize()
+    assert torch.equal(raw, again), "two identical calls differ"
+    raw = raw.cpu()
+    assert raw.shape == (c.Q, 4) and bool(torch.isfinite(raw).all())
+    assert float(raw[:, :3].abs().max()) == 0.0, "the geometry stage wrote colours"
+    assert bool((raw[~c.has, 3] == 0).all()), "a has == 0 row with a feature"
+    pick = lambda f: (f[:, 0] + f[:, 1]) + (f[:, 18] + f[:, 19])
+    cgeo32 = rr.idw_features(c.geo.float(), c.I, c.w.float(), c.has)
+    assert cgeo64.dtype == torch.float64 and cgeo32.dtype == torch.float32
+    rt = _Ratios(f"gather-only/{name}", M_LIBM)
+    rt.check("f0+f1+f18+f19", raw[:, 3], pick(cgeo64), pick(cgeo32))
+    rt.finish()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # inverse-distance weights and features
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""colour decoder: fp16 matrix cores with the 3-term split (mlp_col_v4) against the fp32 MFMA kernel (GLORIE_MLP_F32=1) on
+"""colour decoder: fp16 matrix cores with the 3-term split (mlp_col_v5) against the fp32 MFMA kernel (GLORIE_MLP_F32=1) on
 the reference fixture, and the time of a render pass under both"""
 import os, sys, time
 import numpy as np
