@@ -154,6 +154,9 @@ SIGNATURES = {
     "glorie_depth_l1_workspace": (_sz, [_c_int, _c_int]),
     "glorie_depth_l1_accumulate": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp]),
     "glorie_window_rays": (_c_int, [_vp] * 4 + [_c_int] * 5 + [_c_f] * 4 + [_vp, _vp, _c_f, _c_int] + [_vp] * 6),
+    "glorie_valid_index_build": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "glorie_sample_window_rays": (_c_int, [_vp] * 4 + [_c_int] * 5 + [_c_f] * 4 + [_vp, _vp, _vp, _c_f, _c_int] + [_vp] * 8),
+    "glorie_depth_gate": (_c_int, [_vp, ctypes.c_longlong, _vp, _vp, _vp]),
     "glorie_ingest_color": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     "glorie_ingest_depth": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_f, _c_int, _c_int, _vp, _vp]),
 }

@@ -11,9 +11,9 @@
 // loads, five or six gathers and eleven stores.  No atomics, no host synchronisation, no output sized by the data.
 //
 // The direction is formed in the reference's order with every operation rounded to fp32 on its own (contraction is
-// switched off inside the kernel: the library is built with the compiler's default, and a fused multiply-add would round
-// once where torch rounds twice).
-#include "common.hiph"
+// switched off inside gather_ray, window_rays.hiph, which map_sample.hip shares: the library is built with the compiler's
+// default, and a fused multiply-add would round once where torch rounds twice).
+#include "window_rays.hiph"
 
 using namespace glorie;
 
@@ -28,44 +28,17 @@ window_rays_kernel(const float* const* __restrict__ depth_table, const float* co
                    const int64_t* __restrict__ jj, float const_radius, float* __restrict__ rays_o,
                    float* __restrict__ rays_d, float* __restrict__ depth, float* __restrict__ color,
                    float* __restrict__ radius) {
-  // plain operators with contraction off: the _rn intrinsics are inline functions compiled under the default, and their
-  // products and sums were fused again after inlining
-#pragma clang fp contract(off)
   const int m = blockIdx.x / chunks;                                  // window slot (uniform)
   const int k = (blockIdx.x - m * chunks) * kRayThreads + threadIdx.x;   // ray within the slot
   if (k >= per) return;
   const size_t r = (size_t)m * per + k;
 
-  const float* __restrict__ c = c2ws + 16 * (size_t)m;
-  const float* __restrict__ dmap = depth_table[m];
-  const float* __restrict__ img = image_table[m];
-
   // a draw outside the image cannot read outside a map
   const long long iq = ii[r], jq = jj[r];
   const int i = (int)(iq < 0 ? 0 : (iq > W - 1 ? W - 1 : iq));
   const int j = (int)(jq < 0 ? 0 : (jq > H - 1 ? H - 1 : jq));
-  const size_t pix = (size_t)j * W + i, plane = (size_t)H * W;
-
-  // dirs = ((i - cx) / fx, -(j - cy) / fy, -1);  rays_d[a] = (dirs[0] R[a][0] + dirs[1] R[a][1]) + dirs[2] R[a][2]
-  const float dx = ((float)i - cx) / fx;
-  const float dy = -(((float)j - cy) / fy);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float s = dx * c[4 * a] + dy * c[4 * a + 1];
-    rays_d[3 * r + a] = s + -c[4 * a + 2];                         // dirs[2] = -1: the product is exact
-    rays_o[3 * r + a] = c[4 * a + 3];
-  }
-  depth[r] = dmap[pix];
-  if (chw) {
-    color[3 * r] = img[pix];
-    color[3 * r + 1] = img[plane + pix];
-    color[3 * r + 2] = img[2 * plane + pix];
-  } else {
-    color[3 * r] = img[3 * pix];
-    color[3 * r + 1] = img[3 * pix + 1];
-    color[3 * r + 2] = img[3 * pix + 2];
-  }
-  if (radius) radius[r] = radius_table ? radius_table[m][pix] : const_radius;
+  gather_ray(c2ws + 16 * (size_t)m, depth_table[m], image_table[m], (radius && radius_table) ? radius_table[m] : nullptr,
+             chw, H, W, fx, fy, cx, cy, i, j, r, const_radius, rays_o, rays_d, depth, color, radius);
 }
 
 }  // namespace

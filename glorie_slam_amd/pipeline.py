@@ -21,12 +21,17 @@ from .color_grad import (COLOR_GRAD_THRESHOLD, RADIUS_ADD_MAX, RADIUS_ADD_MIN, R
 from .common import get_rays_from_uv
 from .frontend import Frontend
 from .keyframe_select import final_refine_window, frustum_feature_mask, keyframe_selection_overlap, random_select
+from .map_sample import DRAW_RANGE, ValidIndex, depth_gate, sample_window_rays
 from .motion_filter import MotionFilter
 from .neural_point import deform_points, proxy_render_depth, se3_inv, update_points_pos
 from .render_train import FeatureAdam
 from .warp_loss import MAX_FRAMES as MAX_WARP_FRAMES
 from .warp_loss import FrameTable, pix_warping_loss
 from .window_rays import WindowTable, window_rays
+
+# the master config's learning rates of the mapping stages (cfg['mapping'][init | stage][geometry | color])
+MAPPING_RATES = {"geometry": {"decoders_lr": 0.001, "geometry_lr": 0.03, "color_lr": 0.0},
+                 "color": {"decoders_lr": 0.005, "geometry_lr": 0.005, "color_lr": 0.005}}
 
 
 class _CfgVideo:
@@ -61,7 +66,7 @@ class SequenceRunner:
                  map_iters=20, map_rays=1000, add_stride=8, seed=43, pix_warping=None, w_pix_warp_loss=None,
                  mapping_window_size=None, keyframe_selection_method=None, frustum_feature_selection=None,
                  frustum_edge=None, color_grad_radius=None, pixels_based_on_color_grad=None, bind_npc_with_pose=None,
-                 render_depth=None, use_mono_to_complete=None):
+                 render_depth=None, use_mono_to_complete=None, mapping_schedule=False):
         self.net, self.video, self.cfg = net, video, cfg
         self.npc, self.decoders, self.renderer = npc, decoders, renderer
         dev = cfg["device"]
@@ -147,6 +152,22 @@ class SequenceRunner:
         self._render_views = None             # inside map_keyframe with render_depth: frame -> (depth, c2w) or None
         self.refine_losses = []               # final_refine: (first, last) loss per outer pass
         self.refine_windows = []              # final_refine: the window of every outer pass (keyframe ids)
+        # the reference's mapping schedule (mapper.py:390-515, :598-638), opt-in: every window frame's rays drawn among
+        # its valid pixels and gated by min(10 median, 1.2 max) (map_sample.py), a geometry stage before the colour stage
+        # with the stage's learning rates, and the iteration count scaled by the inserted points.  Off, map_keyframe
+        # runs its one-stage loop unchanged
+        self.mapping_schedule = bool(mapping_schedule)
+        stages = {s: {sub: dict(MAPPING_RATES[sub], **mp.get(s, {}).get(sub, {})) for sub in ("geometry", "color")}
+                  for s in ("init", "stage")}
+        self.schedule = dict(rates=stages, geo_iter_first=int(mp.get("geo_iter_first", 400)),
+                             geo_iter_ratio=float(mp.get("geo_iter_ratio", 0.3)),
+                             min_iter_ratio=float(mp.get("min_iter_ratio", 0.95)),
+                             fix_geo_decoder=bool(mp.get("fix_geo_decoder", True)),
+                             fix_color_decoder=bool(mp.get("fix_color_decoder", False)),
+                             iters_first=int(mp.get("iters_first", map_iters)), iters=int(mp.get("iters", map_iters)),
+                             w_geo_loss=float(mp.get("w_geo_loss", 1.0)), w_color_loss=float(mp.get("w_color_loss", 0.5)),
+                             pixels_adding=int(mp["pixels_adding"]) if mp.get("pixels_adding") else None)
+        self.schedules = []                   # per keyframe mapped on the schedule: (iterations, of them geometry stage)
 
     # ---- tracker.py:33-77 ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -225,7 +246,8 @@ class SequenceRunner:
         pixel-warping term joins the loss (warp_loss.py).  With frustum_feature_selection only the feature rows inside
         the keyframe's frustum are trained (keyframe_select.py; FeatureAdam's row masks).  With bind_npc_with_pose the
         cloud is deformed first; with render_depth the keyframe is inserted on its anchor depth and every window frame
-        trains on its render depth (proxy or aligned mono), and a frame with too few tracker depths is skipped"""
+        trains on its render depth (proxy or aligned mono), and a frame with too few tracker depths is skipped.  With
+        mapping_schedule the iterations follow the reference's schedule instead (_optimize_scheduled)"""
         npc, dec, ren = self.npc, self.decoders, self.renderer
         self._render_views = None
         try:
@@ -242,30 +264,47 @@ class SequenceRunner:
                 ins_view = anchor if anchor is not None else self._keyframe_view(k)
                 query_depth = self._keyframe_view(k)[0] if anchor is not None else None
                 rmaps = self._radius_maps(k, ins_view, query_depth=query_depth) if self.color_grad is not None else None
-                ro, rd, d, col, ii, jj, radius = self._keyframe_rays(k, stride=self.add_stride, view=ins_view,
-                                                                     radius_map=rmaps[0] if rmaps else None)
-                npc.add_neural_points(ro, rd, d, col, k, ii, jj, dynamic_radius=radius)
+                if self.mapping_schedule and self.schedule["pixels_adding"]:
+                    # pixels_adding pixels drawn among the anchor depth's valid ones (mapper.py:297-303)
+                    ro, rd, d, col, radius, ii, jj = self._insertion_samples(k, ins_view, rmaps)
+                else:
+                    ro, rd, d, col, ii, jj, radius = self._keyframe_rays(k, stride=self.add_stride, view=ins_view,
+                                                                         radius_map=rmaps[0] if rmaps else None)
+                added = [npc.add_neural_points(ro, rd, d, col, k, ii, jj, dynamic_radius=radius)]
                 if self.pixels_based_on_color_grad > 0:
-                    self._anchor_grad_points(k, rmaps, view=ins_view)
+                    added.append(self._anchor_grad_points(k, rmaps, view=ins_view))
             if npc.pts_num() == 0:
                 return None
+            if self.mapping_schedule:
+                # frame_pts_add (mapper.py:305-324): one host read per keyframe
+                return self._optimize_scheduled(k, rmaps, sum(int(a) for a in added))
             return self._optimize_keyframe(k, rmaps)
         finally:
             self._render_views = None
             self._read_deform_stats()
 
-    def _mapping_loss(self, ro, rd, d, gt_col, radius, geo, col_f, warp=None):
+    def _mapping_loss(self, ro, rd, d, gt_col, radius, geo, col_f, warp=None, *, stage="color", gate=None, w_geo=None,
+                      w_color=None):
         """the loss of one mapping iteration (mapper.py:497-507) on the feature tables geo / col_f: depth and colour L1
         over the rays that carry a depth and met the cloud, plus the pixel-warping term of the window `warp` (its value is
-        left in warp["value"]), per seen ray -> (loss, rendered depth, rendered colour, seen [N] as float)"""
+        left in warp["value"]), per seen ray -> (loss, rendered depth, rendered colour, seen [N] as float).
+        stage "geometry": rendered without the colour decoder, no colour term (mapper.py:483, :500).  gate: 1 / 0 weights
+        [N] of the depth gate (map_sample.depth_gate), multiplied into `seen`.  w_geo, w_color: the weights of the two L1
+        sums (None: 1 and 0.5)"""
         npc, ren = self.npc, self.renderer
-        depth, _, colour, _, counts = ren.render_batch_ray(npc, self.decoders, rd, ro, self.device, "color", gt_depth=d,
+        depth, _, colour, _, counts = ren.render_batch_ray(npc, self.decoders, rd, ro, self.device, stage, gt_depth=d,
                                                            npc_geo_feats=geo, npc_col_feats=col_f,
                                                            cloud_pos=npc.cloud_pos(), dynamic_r_query=radius)
         # (masked sums instead of `x[seen].sum()`: boolean indexing sizes its result on the host - one device round trip
         # in the forward and one in the backward pass of every iteration)
         seen = ((counts > 0) & (d > 0)).to(depth.dtype)
-        loss = (torch.abs(d - depth) * seen).sum() + 0.5 * (torch.abs(gt_col - colour) * seen[:, None]).sum()
+        if gate is not None:
+            seen = seen * gate
+        loss = (torch.abs(d - depth) * seen).sum()
+        if w_geo is not None:
+            loss = w_geo * loss
+        if stage == "color":
+            loss = loss + (0.5 if w_color is None else w_color) * (torch.abs(gt_col - colour) * seen[:, None]).sum()
         if warp is not None:
             # inside the numerator: its weight relative to the L1 sums is the reference's (mapper.py:497-507)
             w = pix_warping_loss(ro, rd, depth, warp["c2ws"], ren.fx, ren.fy, ren.cx, ren.cy, self.video.wd,
@@ -391,6 +430,127 @@ class SequenceRunner:
         dec.eval()
         self.losses.append((float(first), float(last)))
         if warp is not None:
+            self.warp_losses.append((float(warp["first"]), float(warp["value"])))
+        if frustum is not None:
+            self.frustum_counts.append(int(frustum[1]))
+        return self.losses[-1]
+
+    # ---- the reference's schedule (mapper.py:390-515, :598-638), mapping_schedule=True ------------------------------
+    def _const_radius(self):
+        return 0.5 * (self.npc.radius_add + self.npc.radius_query) if self.npc.use_dynamic_radius else None
+
+    def _insertion_samples(self, k, view, rmaps):
+        """cfg pixels_adding pixels of keyframe k drawn among the valid pixels of its insertion depth, one launch ->
+        (rays_o, rays_d, depth, colour, radius, ii, jj)"""
+        ren = self.renderer
+        table = WindowTable([view[0]], [self.images[k]], view[1][None].float(), [rmaps[0]] if rmaps else None)
+        draws = torch.randint(0, DRAW_RANGE, (self.schedule["pixels_adding"],), generator=self.gen).to(self.device)
+        return sample_window_rays(table, ValidIndex(table), draws, draws.shape[0], ren.fx, ren.fy, ren.cx, ren.cy,
+                                  const_radius=None if rmaps else self._const_radius())
+
+    def schedule_of(self, init, frame_pts_add):
+        """(iterations, of them in the geometry stage) of a keyframe (mapper.py:613-629): iters_first for the first mapped
+        keyframe, else iters scaled by the inserted points over 300, clipped to [min_iter_ratio iters, 2 iters];
+        iteration t is a geometry iteration iff t <= geo_iter_first (first keyframe) or int(n geo_iter_ratio)"""
+        sc = self.schedule
+        if init:
+            n, bound = sc["iters_first"], sc["geo_iter_first"]
+        else:
+            n = min(max(int(sc["iters"] * frame_pts_add / 300), int(sc["min_iter_ratio"] * sc["iters"])), 2 * sc["iters"])
+            bound = int(n * sc["geo_iter_ratio"])
+        return n, min(n, bound + 1)
+
+    def _optimize_scheduled(self, k, rmaps, frame_pts_add):
+        """the mapping iterations of map_keyframe on the reference's schedule.  One WindowTable and ValidIndex per
+        keyframe over its window; every iteration is one sampling launch and one gate launch in front of the loss, its
+        stage and learning rates by schedule_of.  Runs eagerly"""
+        npc, dec, ren, sc = self.npc, self.decoders, self.renderer, self.schedule
+        init = not self.schedules
+        n_it, n_geo = self.schedule_of(init, frame_pts_add)
+        rates = sc["rates"]["init" if init else "stage"]
+        geo = npc.geo_feats.detach().clone().requires_grad_(True)
+        col_f = npc.col_feats.detach().clone().requires_grad_(True)
+        geo_params, col_params = list(dec.geo_decoder.parameters()), list(dec.color_decoder.parameters())
+        flags = [(p, p.requires_grad) for p in dec.parameters()]
+        with torch.no_grad():
+            view = self._keyframe_view(k)
+            win = self._map_window(k, view) if (self.pix_warping or self.keyframe_selection_method) else None
+            warp = win if self.pix_warping else None
+            window = win["window"] if win is not None else [k]
+            views = win["views"] if win is not None else {k: view}
+            per = win["per"] if win is not None else self.map_rays
+            self.windows.append(window)
+            frustum = frustum_feature_mask(npc.cloud_pos(), view[1], view[0], ren.fx, ren.fy, ren.cx, ren.cy,
+                                           self.video.ht, self.video.wd, self.frustum_edge) \
+                if self.frustum_feature_selection else None
+            row_masks = {id(geo): frustum[0], id(col_f): frustum[0]} if frustum is not None else None
+            rq = None
+            if rmaps is not None:
+                rq = [rmaps[1] if f == k else self._radius_maps(f, views[f], add=False)[1] for f in window]
+            table = WindowTable([views[f][0] for f in window], [self.images[f] for f in window],
+                                torch.stack([views[f][1] for f in window]).float(), rq, channels_first=True)
+            index = ValidIndex(table, "all" if self.render_depth == "mono" else "depth")
+            const_r = None if rq is not None else self._const_radius()
+            # every iteration's draws in one transfer
+            draws = torch.randint(0, DRAW_RANGE, (n_it, len(window) * per), generator=self.gen).to(self.device)
+            # one look per keyframe: when every drawn ray is sure to carry a depth the renderer needs no host check
+            all_depth = bool((index.counts > 0).all()) if index.mode == "depth" \
+                else bool(torch.stack([(d > 0).all() for d in table.depths]).all())
+        trained = ([] if sc["fix_geo_decoder"] else geo_params) + ([] if sc["fix_color_decoder"] else col_params)
+        opt = FeatureAdam([{"params": trained, "lr": 0.0}, {"params": [geo], "lr": 0.0}, {"params": [col_f], "lr": 0.0}])
+        self.last_optimizer = opt
+        first = last = None
+        dec.train()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ren.assume_depth = all_depth
+        try:
+            for p in geo_params:
+                p.requires_grad_(not sc["fix_geo_decoder"])
+            for it in range(n_it):
+                stage = "geometry" if it < n_geo else "color"
+                if it in (0, n_geo):
+                    # the colour decoder is not run in the geometry stage: no gradient is formed for it there
+                    for p in col_params:
+                        p.requires_grad_(stage == "color" and not sc["fix_color_decoder"])
+                lrs = rates[stage]
+                for group, key in zip(opt.param_groups, ("decoders_lr", "geometry_lr", "color_lr")):
+                    group["lr"] = float(lrs[key])
+                with torch.no_grad():
+                    ro, rd, d, gt_col, radius, ii, jj = sample_window_rays(table, index, draws[it], per, ren.fx, ren.fy,
+                                                                           ren.cx, ren.cy, const_radius=const_r)
+                    gate, gate_stats = depth_gate(d)
+                opt.zero_grad()
+                loss, depth, colour, seen = self._mapping_loss(
+                    ro, rd, d, gt_col, radius, geo, col_f if stage == "color" else col_f.detach(), warp, stage=stage,
+                    gate=gate, w_geo=sc["w_geo_loss"], w_color=sc["w_color_loss"])
+                if self.map_probe is not None:
+                    self.map_probe(k, dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(), colour=colour.detach(),
+                                           seen=seen, loss=loss.detach(), warp=warp, window=win,
+                                           frustum=frustum[0] if frustum is not None else None, radius=radius,
+                                           pix=torch.stack([ii, jj]), stage=stage, gate=gate, gate_stats=gate_stats, ii=ii,
+                                           jj=jj, lrs=dict(lrs)))
+                loss.backward()
+                opt.step(row_masks=row_masks)
+                last = loss.detach()
+                if first is None:
+                    first = last
+                    if warp is not None:
+                        warp["first"] = warp["value"].clone()
+        finally:
+            ren.assume_depth = False
+            for p, req in flags:
+                p.requires_grad_(req)
+        torch.cuda.synchronize()
+        self.timing["map_iter_ms"].append(1e3 * (time.perf_counter() - t0) / max(n_it, 1))
+        with torch.no_grad():
+            npc.update_geo_feats(geo.detach())
+            npc.update_col_feats(col_f.detach())
+        dec.eval()
+        nan = float("nan")
+        self.losses.append((float(first), float(last)) if n_it else (nan, nan))
+        self.schedules.append((n_it, n_geo))
+        if warp is not None and n_it:
             self.warp_losses.append((float(warp["first"]), float(warp["value"])))
         if frustum is not None:
             self.frustum_counts.append(int(frustum[1]))
@@ -559,8 +719,8 @@ class SequenceRunner:
             radius = torch.full_like(d, 0.5 * (self.npc.radius_add + self.npc.radius_query))
         else:
             radius = None
-        self.npc.add_neural_points(ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous(), d, col.contiguous(),
-                                   k, ii, jj, is_pts_grad=True, dynamic_radius=radius)
+        return self.npc.add_neural_points(ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous(), d,
+                                          col.contiguous(), k, ii, jj, is_pts_grad=True, dynamic_radius=radius)
 
     def _capture_iteration(self, iteration):
         """record one mapping iteration into a hipGraph (one memory pool for all keyframes of this runner, kept open by a

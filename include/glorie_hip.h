@@ -1077,6 +1077,46 @@ int glorie_window_rays(const void* depth_table, const void* image_table, const v
                        float* color, float* radius, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Masked ray sampling and the depth gate (the per-keyframe mapping loop)                */
+/* ------------------------------------------------------------------------------------ */
+
+/* Rank tables of the valid pixels of M depth maps, once per window
+ *   reference: src/utils/common.py:57-77 (select_uv: mask.reshape(-1).nonzero()), src/mapper.py:570-578 (render_mask)
+ * depth_table: DEVICE array of M `const float*`, depth maps [H,W] f32 (not read, may be NULL, with GLORIE_VALID_ALL).
+ * Pixel p = j * W + i is valid iff depth[p] > 0 (NaN and negative depths are invalid); GLORIE_VALID_ALL: every pixel.
+ * words uint64 [M, nw], nw = ceil(H W / 64): bit p % 64 of word p / 64, the tail bits of the last word zero.
+ * prefix int32 [M, nw + 1]: prefix[m][w] = the valid pixels of frame m below word w, prefix[m][nw] = its valid count.
+ * H W <= 2^31 - 4097.  M = 0 launches nothing.  One launch (one workgroup per frame), no atomics, no host synchronisation. */
+#define GLORIE_VALID_DEPTH 0
+#define GLORIE_VALID_ALL 1
+int glorie_valid_index_build(const void* depth_table, int M, int H, int W, int mode, uint64_t* words, int32_t* prefix,
+                             void* stream);
+
+/* The rays of one training iteration over M keyframes, every slot's pixels drawn among its valid pixels
+ *   reference: src/mapper.py:427-431 (get_samples(..., mask=render_mask)), src/utils/common.py:57-145
+ * The arguments of glorie_window_rays with ii, jj replaced by draws int64 [N] in [0, 2^31) (clamped to it), N = M * per,
+ * frame-major, and the tables of glorie_valid_index_build for the same M, H, W.  Ray r of slot m = r / per takes
+ * rank = (draws[r] * count_m) >> 31 in int64, count_m = prefix[m][nw]; its pixel p is the rank-th valid pixel of the slot
+ * in row-major order, i = p % W, j = p / W.  rays_o, rays_d, depth, color, radius are what glorie_window_rays writes for
+ * that pixel, bit for bit; ii, jj int64 [N] receive the pixel.  A slot with count_m = 0 yields pixel (0, 0) and
+ * depth 0 for all its rays.  N = 0 launches nothing.  One launch, no atomics, no host synchronisation. */
+int glorie_sample_window_rays(const void* depth_table, const void* image_table, const void* radius_table, const float* c2ws,
+                              int M, int per, int chw, int H, int W, float fx, float fy, float cx, float cy,
+                              const int64_t* draws, const uint64_t* words, const int32_t* prefix, float const_radius,
+                              int want_radius, float* rays_o, float* rays_d, float* depth, float* color, float* radius,
+                              int64_t* ii, int64_t* jj, void* stream);
+
+/* The outlier gate of one iteration's rays as weights
+ *   reference: src/mapper.py:474-482 (inside_mask = depth <= min(10 * depth.median(), 1.2 * depth.max()))
+ * depth f32 [N] -> keep f32 [N] (1 / 0), stats f32 [4] = (median, max, threshold, kept count).  The median is the lower
+ * median (sorted rank (n_pos - 1) / 2, as torch.median) and the max the maximum of the n_pos entries with depth > 0 (NaN
+ * is not among them); threshold = fminf(10.0f * median, 1.2f * max), each product rounded once;
+ * keep = depth > 0 && depth <= threshold.  n_pos = 0: keep and stats are all 0.  Exact (a radix select over the float
+ * bits).  N = 0 launches nothing and leaves stats alone; N > 2^22: GLORIE_EUNSUPPORTED.  One launch of one workgroup,
+ * no atomics, no host synchronisation. */
+int glorie_depth_gate(const float* depth, long long N, float* keep, float* stats, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Frame ingest (dataset streams)                                                        */
 /* ------------------------------------------------------------------------------------ */
 
