@@ -159,6 +159,11 @@ SIGNATURES = {
     "glorie_depth_gate": (_c_int, [_vp, ctypes.c_longlong, _vp, _vp, _vp]),
     "glorie_ingest_color": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     "glorie_ingest_depth": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_f, _c_int, _c_int, _vp, _vp]),
+    "glorie_vis_ranges_workspace": (_sz, []),
+    "glorie_vis_ranges": (_c_int, [_vp, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp]),
+    "glorie_vis_sheet_size": (_c_int, [_c_int] * 5 + [ctypes.POINTER(_c_int)] * 2),
+    "glorie_vis_compose": (_c_int, [_vp] * 9 + [_c_int, _c_int, _vp, _c_f, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
+    "glorie_vis_rgb8": (_c_int, [_vp, ctypes.c_longlong, _vp, _vp]),
 }
 
 _lib = None

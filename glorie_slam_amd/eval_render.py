@@ -11,9 +11,12 @@ Both return {"frames": [{"video_idx", "tstamp", "psnr", "ms_ssim", "masked_psnr"
 The per-frame values stay on the device and are read back once at the end; the runner, its images and the cloud are only
 read.
 
-Out of scope: LPIPS (torchmetrics' AlexNet weights come from the network) and the PNG copies of the renders (cv2); the
-metrics files keep the reference's names and line order minus the LPIPS lines.  The mesh that reads the saved maps:
-generate_mesh.py.
+With save_png the unmasked render of every frame is also written as a PNG, as the reference does through cv2
+(eval_render.py:54-57, :178-181): rerendered_keyframe_image/frame_%05d.png for the keyframes, rerendered_image/frame_%05d.png
+for eval_imgs, the bytes of visualizer.to_rgb8 (saturate(rint(255 x)), RGB), written with PIL.
+
+Out of scope: LPIPS (torchmetrics' AlexNet weights come from the network); the metrics files keep the reference's names
+and line order minus the LPIPS lines.  The mesh that reads the saved maps: generate_mesh.py.
 """
 import os
 import shutil
@@ -50,9 +53,15 @@ def _score(runner, c2w, render_depth, r_query, gt_color, gt_depth):
     return frame_metrics(color, depth, gt_color, mask, gt_depth=gt_depth), color, depth, mask
 
 
-def _evaluate(runner, views, output, subdir, log_name, ssim_label, gt_depth_fn, keep_renders):
-    """views: iterable of (video_idx or None, tstamp, gt_color [H,W,3], c2w, render_depth [H,W], r_query [H,W] or None)"""
+def _evaluate(runner, views, output, subdir, log_name, ssim_label, gt_depth_fn, keep_renders, png_subdir=None):
+    """views: iterable of (video_idx or None, tstamp, gt_color [H,W,3], c2w, render_depth [H,W], r_query [H,W] or None);
+    png_subdir: with `output`, the directory under it that receives frame_%05d.png of every unmasked render"""
     dev = runner.device
+    png_dir = None
+    if output is not None and png_subdir is not None:
+        from .visualizer import save_image, to_rgb8
+        png_dir = os.path.join(str(output), png_subdir)
+        os.makedirs(png_dir, exist_ok=True)
     if output is not None:
         maps_dir = os.path.join(str(output), subdir)
         if os.path.exists(maps_dir):
@@ -73,6 +82,8 @@ def _evaluate(runner, views, output, subdir, log_name, ssim_label, gt_depth_fn, 
             if output is not None:
                 np.save(os.path.join(maps_dir, f"depth_{int(tstamp):05d}"), m["depth"].cpu().numpy())
                 np.save(os.path.join(maps_dir, f"color_{int(tstamp):05d}"), m["color"].cpu().numpy())
+            if png_dir is not None:
+                save_image(os.path.join(png_dir, f"frame_{int(tstamp):05d}.png"), to_rgb8(color))
     values = torch.stack(rows).double().cpu().numpy() if rows else np.zeros((0, len(keys)))      # the one read-back
     for frame, row in zip(frames, values):
         frame.update({k: float(v) for k, v in zip(keys, row)})
@@ -88,14 +99,15 @@ def _evaluate(runner, views, output, subdir, log_name, ssim_label, gt_depth_fn, 
     return out
 
 
-def eval_kf_imgs(runner, output=None, gt_depth_fn=None, keep_renders=False):
+def eval_kf_imgs(runner, output=None, gt_depth_fn=None, keep_renders=False, save_png=False):
     """eval_kf_imgs (eval_render.py:18-124) over the mapped keyframes of a SequenceRunner that were not skipped.  Each is
     rendered on the view the mapper trained it on - with render_depth its proxy / aligned mono depth, else the tracker's
     depth - with its own dynamic_r_query / 3 * render_depth when the colour-gradient radii are on.  The mask is
     valid_ray_mask > 0 & render_depth > 0 (& gt_depth > 0 when gt_depth_fn(tstamp) -> [H,W] is given; without it
     depth_l1 is left out).  output: writes rendered_every_keyframe/{depth,color}_%05d.npy (the masked maps, by
     timestamp) and logs/metrics_render_kf.txt.  keep_renders: every frame also carries "render" = the unmasked colour,
-    the depth and the mask as device tensors"""
+    the depth and the mask as device tensors.  save_png with output: rerendered_keyframe_image/frame_%05d.png, the
+    unmasked render colour of every keyframe (by timestamp)"""
     def views():
         for k in range(runner.mapped):
             if k in runner.skipped:
@@ -115,16 +127,17 @@ def eval_kf_imgs(runner, output=None, gt_depth_fn=None, keep_renders=False):
             yield k, float(runner.video.timestamp[k]), gt_color, c2w, render_depth, r_query
 
     return _evaluate(runner, views(), output, "rendered_every_keyframe", "metrics_render_kf.txt", "ssim", gt_depth_fn,
-                     keep_renders)
+                     keep_renders, "rerendered_keyframe_image" if save_png else None)
 
 
-def eval_imgs(runner, frames, est_c2ws, every_frame, output=None, gt_depth_fn=None, keep_renders=False):
+def eval_imgs(runner, frames, est_c2ws, every_frame, output=None, gt_depth_fn=None, keep_renders=False, save_png=False):
     """eval_imgs (eval_render.py:126-247): frames is an iterable of (idx, image [1,3,H,W] or [3,H,W] in [0,1]), est_c2ws[idx]
     the estimated camera-to-world matrix [4,4] (OpenCV convention, flipped to OpenGL here); every `every_frame`-th frame
     is rendered on the depth of the projected cloud (proj_depth_map; the neural points when the runner keeps no
     unprojected keyframe maps), its holes filled from the mono prior aligned on the projected pixels
     (align_scale_and_shift), with the query radii of the frame's own colour gradients.  output: writes
-    rendered_every_frame/{depth,color}_%05d.npy and logs/metrics_render_every.txt"""
+    rendered_every_frame/{depth,color}_%05d.npy and logs/metrics_render_every.txt, and with save_png
+    rerendered_image/frame_%05d.png, the unmasked render colour of every rendered frame"""
     dev = runner.device
     cfg = runner._mono_cfg()
     cfg["mapping"] = dict(cfg["mapping"], mapping_window_size=runner.mapping_window_size)
@@ -154,4 +167,4 @@ def eval_imgs(runner, frames, est_c2ws, every_frame, output=None, gt_depth_fn=No
             yield None, float(idx), image.permute(1, 2, 0).contiguous(), c2w, render_depth, r_query
 
     return _evaluate(runner, views(), output, "rendered_every_frame", "metrics_render_every.txt", "msssim", gt_depth_fn,
-                     keep_renders)
+                     keep_renders, "rerendered_image" if save_png else None)

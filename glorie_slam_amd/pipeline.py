@@ -66,7 +66,8 @@ class SequenceRunner:
                  map_iters=20, map_rays=1000, add_stride=8, seed=43, pix_warping=None, w_pix_warp_loss=None,
                  mapping_window_size=None, keyframe_selection_method=None, frustum_feature_selection=None,
                  frustum_edge=None, color_grad_radius=None, pixels_based_on_color_grad=None, bind_npc_with_pose=None,
-                 render_depth=None, use_mono_to_complete=None, mapping_schedule=False):
+                 render_depth=None, use_mono_to_complete=None, mapping_schedule=False, mapping_vis=None,
+                 save_rendered_image=None):
         self.net, self.video, self.cfg = net, video, cfg
         self.npc, self.decoders, self.renderer = npc, decoders, renderer
         dev = cfg["device"]
@@ -168,6 +169,17 @@ class SequenceRunner:
                              w_geo_loss=float(mp.get("w_geo_loss", 1.0)), w_color_loss=float(mp.get("w_color_loss", 0.5)),
                              pixels_adding=int(mp["pixels_adding"]) if mp.get("pixels_adding") else None)
         self.schedules = []                   # per keyframe mapped on the schedule: (iterations, of them geometry stage)
+        # the per-keyframe contact sheet (mapper.py:664-673, visualizer.py), opt-in: mapping_vis is a directory, or True
+        # for <output>/mapping_vis with `output` the run's directory (run(output=...) or the attribute); with
+        # save_rendered_image (the argument, else cfg["mapping"]["save_rendered_image"]) the rendered colour goes to
+        # rendered_image/ next to it.  Off, nothing below is touched
+        self.mapping_vis = None if mapping_vis in (None, False) else mapping_vis
+        self.save_rendered_image = bool(mp.get("save_rendered_image", False) if save_rendered_image is None
+                                        else save_rendered_image)
+        self.output = None
+        self.visualizer = None                # created with the first sheet
+        self.vis_options = {}                 # Visualizer keywords (scale, gutter, title, titles, keep, logger)
+        self._vis_depths = None               # with render_depth: (aligned mono prior, tracker depth) of the keyframe
 
     # ---- tracker.py:33-77 ------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -247,9 +259,11 @@ class SequenceRunner:
         the keyframe's frustum are trained (keyframe_select.py; FeatureAdam's row masks).  With bind_npc_with_pose the
         cloud is deformed first; with render_depth the keyframe is inserted on its anchor depth and every window frame
         trains on its render depth (proxy or aligned mono), and a frame with too few tracker depths is skipped.  With
-        mapping_schedule the iterations follow the reference's schedule instead (_optimize_scheduled)"""
+        mapping_schedule the iterations follow the reference's schedule instead (_optimize_scheduled).  With mapping_vis
+        the keyframe's contact sheet is written after its last iteration (_visualize)"""
         npc, dec, ren = self.npc, self.decoders, self.renderer
         self._render_views = None
+        self._vis_depths = None
         try:
             with torch.no_grad():
                 if self.bind_npc_with_pose and npc.pts_num() > 0:
@@ -433,6 +447,8 @@ class SequenceRunner:
             self.warp_losses.append((float(warp["first"]), float(warp["value"])))
         if frustum is not None:
             self.frustum_counts.append(int(frustum[1]))
+        if self.mapping_vis is not None:
+            self._visualize(k, view, rq[k] if rq else None, self.map_iters)
         return self.losses[-1]
 
     # ---- the reference's schedule (mapper.py:390-515, :598-638), mapping_schedule=True ------------------------------
@@ -554,7 +570,43 @@ class SequenceRunner:
             self.warp_losses.append((float(warp["first"]), float(warp["value"])))
         if frustum is not None:
             self.frustum_counts.append(int(frustum[1]))
+        if self.mapping_vis is not None:
+            self._visualize(k, view, rq[-1] if rq else None, n_it)
         return self.losses[-1]
+
+    # ---- the per-keyframe contact sheet (mapper.py:664-673) --------------------------------------------------------
+    def _visualize(self, k, view, r_query, n_it):
+        """Visualizer.vis for keyframe k after its last iteration: the view it trained on, its query radii and the
+        trained feature tables (already back in the cloud); the tracker depth and the mono prior are the render-depth
+        path's (aligned prior) or, without render_depth, the view depth itself and the raw prior.  Only reads"""
+        import os
+
+        from .visualizer import Visualizer
+        npc = self.npc
+        if self.visualizer is None:
+            vis_dir = self.mapping_vis
+            if vis_dir is True:
+                if self.output is None:
+                    raise ValueError("mapping_vis=True needs the run's output directory (run(output=...) or .output)")
+                vis_dir = os.path.join(str(self.output), "mapping_vis")
+            base = str(self.output) if self.output is not None else os.path.dirname(os.path.abspath(str(vis_dir)))
+            self.visualizer = Visualizer(str(vis_dir), self.renderer, False, device=self.device,
+                                         img_dir=os.path.join(base, "rendered_image"), **self.vis_options)
+        with torch.no_grad():
+            render_depth, c2w = view
+            if self._vis_depths is not None:
+                mono, droid = self._vis_depths
+            else:
+                mono, droid = self._mono_prior(k), render_depth
+            if r_query is None and npc.use_dynamic_radius:
+                r_query = torch.full_like(render_depth, 0.5 * (npc.radius_add + npc.radius_query))
+            cfg = self._mono_cfg()
+            cfg["mapping"] = dict(cfg["mapping"], mapping_window_size=self.mapping_window_size)
+            self.visualizer.vis(int(self.video.timestamp[k]), n_it - 1, None, render_depth, droid, mono,
+                                self.images[k].permute(1, 2, 0).contiguous(), c2w, npc, self.decoders,
+                                npc.get_geo_feats(), npc.get_col_feats(), cfg, None, freq_override=(k == 0),
+                                dynamic_r_query=r_query, cloud_pos=npc.cloud_pos(), cur_total_iters=n_it,
+                                save_rendered_image=self.save_rendered_image)
 
     # ---- deformation and render depth (mapper.py:246-279, :557-573, :705-730) -------------------------------------
     def _deform(self):
@@ -639,6 +691,8 @@ class SequenceRunner:
         if got is None:
             return None
         c2w, m_wq, droid = got
+        if self.mapping_vis is not None:
+            self._vis_depths = (m_wq, droid)
         anchor = torch.where(droid == 0, m_wq, droid) if self.render_depth == "proxy" else m_wq.clone()
         if self.npc.video is None:
             self.npc.video = self.video
@@ -888,9 +942,12 @@ class SequenceRunner:
                   rgb.astype(np.float64) / 255.0)
 
     # ---- the stream -------------------------------------------------------------------------------------------------
-    def run(self, frames, intrinsics, final_ba_steps=7, final_refine=False):
+    def run(self, frames, intrinsics, final_ba_steps=7, final_refine=False, output=None):
         """frames: iterable of (tstamp, image [1,3,H,W] in [0,1]).  final_refine: the final refinement of the map
-        (final_refine() with its defaults) after the final BA.  Returns a summary dict."""
+        (final_refine() with its defaults) after the final BA.  output: the run's directory, where mapping_vis=True puts
+        mapping_vis/ and rendered_image/.  Returns a summary dict."""
+        if output is not None:
+            self.output = output
         for tstamp, image in frames:
             self.track(tstamp, image, intrinsics)
             self.map_pending()

@@ -1147,6 +1147,47 @@ int glorie_ingest_color(const uint8_t* frames, int B, int H, int W, const int32_
 int glorie_ingest_depth(const void* raw, int dtype, int B, int H, int W, const int32_t* ysrc, const int32_t* xsrc,
                         float scale, int H_out, int W_out, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* The mapper's per-keyframe contact sheet                                                */
+/* ------------------------------------------------------------------------------------ */
+
+/* The three data-dependent ranges of the sheet   reference: src/utils/Visualizer.py:121-123, :132, :144
+ * render_depth, depth, droid_depth f32 [n] -> ranges f32 [4] = (dmax, rmin, rmax, 0):
+ *   dmax       = max(droid_depth)
+ *   rmin, rmax = min and max of res = min(|render_depth - depth|, 0.2), with res = 0 where render_depth == 0 and a NaN kept
+ * Non-finite values are skipped; a range nothing went into is 0, and a zero is written as +0.  Order-free, hence exact.
+ * workspace: glorie_vis_ranges_workspace() bytes, 4-byte aligned, need not be initialised.  n = 0 gives (0, 0, 0, 0).  Two
+ * launches, no atomics, no host synchronisation. */
+size_t glorie_vis_ranges_workspace(void);
+int glorie_vis_ranges(const float* render_depth, const float* depth, const float* droid_depth, long long n, float* ranges,
+                      void* workspace, void* stream);
+
+/* The size of the sheet: ph = ceil(H / scale), pw = ceil(W / scale), SH = gutter + 4 (title + ph + gutter),
+ * SW = gutter + 3 (pw + gutter).  Panel k = 3 r + c has its first pixel at row gutter + r (title + ph + gutter) + title,
+ * column gutter + c (pw + gutter); the title rows above it are left white for the caller.  Host only. */
+int glorie_vis_sheet_size(int H, int W, int scale, int gutter, int title, int* SH, int* SW);
+
+/* The whole sheet, one launch   reference: src/utils/Visualizer.py:118-203
+ * sheet uint8 [SH,SW,3] (RGB) from f32 maps [H,W] (color, gt_color: [H,W,3]); every byte is written, what is no panel is
+ * 255.  Panel pixel (y, x) shows source pixel s = (min(y scale + scale / 2, H-1), min(x scale + scale / 2, W-1)).
+ * Scalar panels go through table uint8 [256,3]: t = (v - vmin) / (vmax - vmin) (IEEE division; 0 when vmin == vmax),
+ * entry clamp(trunc(256 t), 0, 255) (a NaN t: entry 0); a non-finite v is white.  Colour panels write
+ * lvl(x) = trunc(255 clamp(x, 0, 1)) per channel (a NaN x: 0).  With (dmax, rmin, rmax) = ranges[0..2], all in float32:
+ *    0 render_depth [0,dmax]     1 depth [0,dmax]                       2 res (as above) [rmin,rmax]
+ *    3 lvl(gt_color)             4 lvl(c), c = rint(255 color) / 255    5 lvl(|gt_color - c|), 0 where render_depth == 0
+ *    6 droid_depth [0,dmax]      7 proj_depth [0,dmax]                  8 proj_depth > 0 [0,1]
+ *    9 valid_count [0,count_max] 10 sparse_depth [0,dmax]               11 mono_depth [0,dmax]
+ * ranges is read on the device.  No workspace, no atomics, no host synchronisation. */
+int glorie_vis_compose(const float* render_depth, const float* depth, const float* color, const float* gt_color,
+                       const float* droid_depth, const float* proj_depth, const float* valid_count,
+                       const float* sparse_depth, const float* mono_depth, int H, int W, const float* ranges,
+                       float count_max, const uint8_t* table, int scale, int gutter, int title, uint8_t* sheet,
+                       void* stream);
+
+/* Float colour -> bytes: out[i] = saturate(rint(255 color[i])) (ties to even, NaN -> 0), what cv2.imwrite stores of a float
+ * image (Visualizer.py:108-112, eval_render.py:54-57).  color f32 [n] -> out uint8 [n].  One launch. */
+int glorie_vis_rgb8(const float* color, long long n, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
