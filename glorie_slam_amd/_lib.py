@@ -131,6 +131,10 @@ SIGNATURES = {
     "glorie_frame_reduce_workspace": (_sz, [_c_int, _c_int]),
     "glorie_frame_reduce": (_c_int, [_vp, _vp, _c_int, _c_int] + [_vp] * 7),
     "glorie_mask_apply": (_c_int, [_vp, _c_int, _c_int] + [_vp] * 7),
+    "glorie_lpips_weight_floats": (_sz, []),
+    "glorie_lpips_shapes": (_c_int, [_c_int, _c_int, ctypes.POINTER(_c_int)]),
+    "glorie_lpips_workspace": (_sz, [_c_int, _c_int]),
+    "glorie_lpips": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_int, _vp]),
     "glorie_tsdf_allocate_workspace": (_sz, [ctypes.c_long]),
     "glorie_tsdf_allocate": (_c_int, [_vp, _c_int, _c_int, _vp] + [_c_f] * 6 + [_vp, _c_f, _vp, _vp, _vp, _c_int, _vp, _vp,
                                       ctypes.POINTER(_c_int), _vp]),

@@ -50,20 +50,6 @@ __device__ __forceinline__ size_t pixel_index(int hwc, int c, int y, int x, int 
   return hwc ? ((size_t)y * w + x) * 3 + c : ((size_t)c * h + y) * w + x;
 }
 
-// Sum of n doubles p[0], p[stride], ... by one wave, in a fixed order: lane i adds its contiguous run of ceil(n / 64)
-// elements in index order, then every lane adds the 64 run sums in lane order (the same value in every lane)
-__device__ __forceinline__ double ordered_sum(const double* __restrict__ p, int n, int stride) {
-  const int lane = threadIdx.x & 63;
-  const int run = (n + 63) / 64;
-  const int j0 = min(n, lane * run), j1 = min(n, j0 + run);
-  double s = 0.0;
-  for (int j = j0; j < j1; ++j) s += p[(size_t)j * stride];
-  double t = 0.0;
-#pragma unroll
-  for (int i = 0; i < 64; ++i) t += __shfl(s, i, 64);
-  return t;
-}
-
 // 2x2 average pooling of one channel of x and y into the planar next level; input index 2o - pad, 2o - pad + 1
 __device__ __forceinline__ float pool_at(const float* __restrict__ img, int hwc, int c, int h, int w, int oy, int ox) {
   const int y0 = 2 * oy - (h & 1), x0 = 2 * ox - (w & 1);

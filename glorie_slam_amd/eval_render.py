@@ -6,7 +6,8 @@ image_metrics.py; the masked depth and colour maps that meshing reads and the me
   eval_kf_imgs(runner)                                   the keyframes, on the view the mapper trained on
   eval_imgs(runner, frames, est_c2ws, every_frame)       arbitrary frames with given poses, on the projected cloud depth
 
-Both return {"frames": [{"video_idx", "tstamp", "psnr", "ms_ssim", "masked_psnr", "masked_ms_ssim"[, "depth_l1"]}],
+Both return {"frames": [{"video_idx", "tstamp", "psnr", "ms_ssim", "masked_psnr", "masked_ms_ssim"[, "depth_l1"][, "lpips",
+"masked_lpips"]}],
 "avg_psnr", "avg_ms_ssim", "avg_masked_psnr", "avg_masked_ms_ssim", "avg_depth_l1" (None without gt depth), "frame_cnt"}.
 The per-frame values stay on the device and are read back once at the end; the runner, its images and the cloud are only
 read.
@@ -15,8 +16,11 @@ With save_png the unmasked render of every frame is also written as a PNG, as th
 (eval_render.py:54-57, :178-181): rerendered_keyframe_image/frame_%05d.png for the keyframes, rerendered_image/frame_%05d.png
 for eval_imgs, the bytes of visualizer.to_rgb8 (saturate(rint(255 x)), RGB), written with PIL.
 
-Out of scope: LPIPS (torchmetrics' AlexNet weights come from the network); the metrics files keep the reference's names
-and line order minus the LPIPS lines.  The mesh that reads the saved maps: generate_mesh.py.
+LPIPS (eval_render.py:27-28, :64-65, :85-86) needs AlexNet's weights, which torchmetrics fetches from the network and this
+package does not: with lpips = an lpips.Lpips built from the caller's weights every frame also carries "lpips" and
+"masked_lpips", the result "avg_lpips" and "avg_masked_lpips", and the metrics files the reference's avg_masked_lpips /
+avg_lpips lines in its line order.  Without it (the default) they keep the reference's names and order minus those
+lines.  The mesh that reads the saved maps: generate_mesh.py.
 """
 import os
 import shutil
@@ -30,6 +34,7 @@ from .image_metrics import frame_metrics
 from .neural_point import proj_depth_map
 
 _KEYS = ("psnr", "ms_ssim", "masked_psnr", "masked_ms_ssim", "depth_l1")
+_LPIPS_KEYS = ("lpips", "masked_lpips")
 
 
 def _constant_radius(runner, like):
@@ -40,7 +45,7 @@ def _constant_radius(runner, like):
     return torch.full_like(like, 0.5 * (npc.radius_add + npc.radius_query))
 
 
-def _score(runner, c2w, render_depth, r_query, gt_color, gt_depth):
+def _score(runner, c2w, render_depth, r_query, gt_color, gt_depth, lpips=None):
     """render one view and score it: (metrics of frame_metrics, unmasked render colour, render depth, mask)"""
     ren, npc = runner.renderer, runner.npc
     depth, _, color, valid_ray_mask, _ = ren.render_img(npc, runner.decoders, c2w, runner.device, stage="color",
@@ -50,10 +55,10 @@ def _score(runner, c2w, render_depth, r_query, gt_color, gt_depth):
     mask = (valid_ray_mask > 0) & (render_depth > 0)
     if gt_depth is not None:
         mask = mask & (gt_depth > 0)
-    return frame_metrics(color, depth, gt_color, mask, gt_depth=gt_depth), color, depth, mask
+    return frame_metrics(color, depth, gt_color, mask, gt_depth=gt_depth, lpips=lpips), color, depth, mask
 
 
-def _evaluate(runner, views, output, subdir, log_name, ssim_label, gt_depth_fn, keep_renders, png_subdir=None):
+def _evaluate(runner, views, output, subdir, log_name, ssim_label, gt_depth_fn, keep_renders, png_subdir=None, lpips=None):
     """views: iterable of (video_idx or None, tstamp, gt_color [H,W,3], c2w, render_depth [H,W], r_query [H,W] or None);
     png_subdir: with `output`, the directory under it that receives frame_%05d.png of every unmasked render"""
     dev = runner.device
@@ -69,11 +74,13 @@ def _evaluate(runner, views, output, subdir, log_name, ssim_label, gt_depth_fn, 
         os.makedirs(maps_dir)
         os.makedirs(os.path.join(str(output), "logs"), exist_ok=True)
     keys = _KEYS if gt_depth_fn is not None else _KEYS[:4]
+    if lpips is not None:
+        keys = keys + _LPIPS_KEYS
     frames, rows = [], []
     with torch.no_grad():
         for video_idx, tstamp, gt_color, c2w, render_depth, r_query in views:
             gt_depth = gt_depth_fn(tstamp).to(dev, torch.float32) if gt_depth_fn is not None else None
-            m, color, depth, mask = _score(runner, c2w, render_depth, r_query, gt_color, gt_depth)
+            m, color, depth, mask = _score(runner, c2w, render_depth, r_query, gt_color, gt_depth, lpips)
             rows.append(torch.stack([m[k] for k in keys]))
             frame = {"video_idx": video_idx, "tstamp": tstamp}
             if keep_renders:
@@ -92,14 +99,17 @@ def _evaluate(runner, views, output, subdir, log_name, ssim_label, gt_depth_fn, 
         for j, k in enumerate(keys):
             out[f"avg_{k}"] = float(values[:, j].sum() / len(frames)) if frames else float("nan")
     if output is not None:
+        masked_lpips = f"avg_masked_lpips: {out['avg_masked_lpips']}\n" if lpips is not None else ""
+        full_lpips = f"avg_lpips: {out['avg_lpips']}\n" if lpips is not None else ""
         text = (f"avg_masked_{ssim_label}: {out['avg_masked_ms_ssim']}\navg_masked_psnr: {out['avg_masked_psnr']}\n"
-                f"###############\navg_{ssim_label}: {out['avg_ms_ssim']}\navg_psnr: {out['avg_psnr']}\n###############\n")
+                f"{masked_lpips}###############\navg_{ssim_label}: {out['avg_ms_ssim']}\navg_psnr: {out['avg_psnr']}\n"
+                f"{full_lpips}###############\n")
         with open(os.path.join(str(output), "logs", log_name), "w+") as fp:
             fp.write(text)
     return out
 
 
-def eval_kf_imgs(runner, output=None, gt_depth_fn=None, keep_renders=False, save_png=False):
+def eval_kf_imgs(runner, output=None, gt_depth_fn=None, keep_renders=False, save_png=False, lpips=None):
     """eval_kf_imgs (eval_render.py:18-124) over the mapped keyframes of a SequenceRunner that were not skipped.  Each is
     rendered on the view the mapper trained it on - with render_depth its proxy / aligned mono depth, else the tracker's
     depth - with its own dynamic_r_query / 3 * render_depth when the colour-gradient radii are on.  The mask is
@@ -107,7 +117,7 @@ def eval_kf_imgs(runner, output=None, gt_depth_fn=None, keep_renders=False, save
     depth_l1 is left out).  output: writes rendered_every_keyframe/{depth,color}_%05d.npy (the masked maps, by
     timestamp) and logs/metrics_render_kf.txt.  keep_renders: every frame also carries "render" = the unmasked colour,
     the depth and the mask as device tensors.  save_png with output: rerendered_keyframe_image/frame_%05d.png, the
-    unmasked render colour of every keyframe (by timestamp)"""
+    unmasked render colour of every keyframe (by timestamp).  lpips: an lpips.Lpips adds the LPIPS values and lines"""
     def views():
         for k in range(runner.mapped):
             if k in runner.skipped:
@@ -127,17 +137,19 @@ def eval_kf_imgs(runner, output=None, gt_depth_fn=None, keep_renders=False, save
             yield k, float(runner.video.timestamp[k]), gt_color, c2w, render_depth, r_query
 
     return _evaluate(runner, views(), output, "rendered_every_keyframe", "metrics_render_kf.txt", "ssim", gt_depth_fn,
-                     keep_renders, "rerendered_keyframe_image" if save_png else None)
+                     keep_renders, "rerendered_keyframe_image" if save_png else None, lpips=lpips)
 
 
-def eval_imgs(runner, frames, est_c2ws, every_frame, output=None, gt_depth_fn=None, keep_renders=False, save_png=False):
+def eval_imgs(runner, frames, est_c2ws, every_frame, output=None, gt_depth_fn=None, keep_renders=False, save_png=False,
+              lpips=None):
     """eval_imgs (eval_render.py:126-247): frames is an iterable of (idx, image [1,3,H,W] or [3,H,W] in [0,1]), est_c2ws[idx]
     the estimated camera-to-world matrix [4,4] (OpenCV convention, flipped to OpenGL here); every `every_frame`-th frame
     is rendered on the depth of the projected cloud (proj_depth_map; the neural points when the runner keeps no
     unprojected keyframe maps), its holes filled from the mono prior aligned on the projected pixels
     (align_scale_and_shift), with the query radii of the frame's own colour gradients.  output: writes
     rendered_every_frame/{depth,color}_%05d.npy and logs/metrics_render_every.txt, and with save_png
-    rerendered_image/frame_%05d.png, the unmasked render colour of every rendered frame"""
+    rerendered_image/frame_%05d.png, the unmasked render colour of every rendered frame.  lpips: an lpips.Lpips adds the
+    LPIPS values and lines"""
     dev = runner.device
     cfg = runner._mono_cfg()
     cfg["mapping"] = dict(cfg["mapping"], mapping_window_size=runner.mapping_window_size)
@@ -167,4 +179,4 @@ def eval_imgs(runner, frames, est_c2ws, every_frame, output=None, gt_depth_fn=No
             yield None, float(idx), image.permute(1, 2, 0).contiguous(), c2w, render_depth, r_query
 
     return _evaluate(runner, views(), output, "rendered_every_frame", "metrics_render_every.txt", "msssim", gt_depth_fn,
-                     keep_renders, "rerendered_image" if save_png else None)
+                     keep_renders, "rerendered_image" if save_png else None, lpips=lpips)

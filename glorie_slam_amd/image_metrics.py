@@ -4,12 +4,14 @@ src/utils/eval_render.py:59-89, which calls pytorch_msssim.ms_ssim and torch's m
   ms_ssim        MS-SSIM of two images with the defaults of pytorch_msssim (glorie_ms_ssim: levels + 1 launches)
   psnr           -10 log10 of the mean squared difference, over the frame or over a mask (glorie_frame_reduce: 2 launches)
   frame_metrics  everything eval_kf_imgs reports for one frame: psnr, ms_ssim, their masked forms, depth L1 and the masked
-                 maps (glorie_frame_reduce, glorie_mask_apply, glorie_ms_ssim twice)
+                 maps (glorie_frame_reduce, glorie_mask_apply, glorie_ms_ssim twice); with an lpips.Lpips also lpips
+                 and masked_lpips (glorie_lpips twice)
 
 Every sum is accumulated in fp64 from per-workgroup partials in a fixed order: repeated calls are bitwise equal, nothing
 reads the device back, and every call records into a hipGraph.  Results are 0-dim float32 device tensors.
 
-Out of scope: LPIPS (torchmetrics' AlexNet weights come from the network) and the PNG copies of the renders (cv2).
+LPIPS is lpips.Lpips, built from weights the caller hands in (torchmetrics fetches AlexNet's from the network, this
+package fetches nothing); without one the LPIPS values are left out.  Out of scope: the PNG copies of the renders (cv2).
 """
 import torch
 
@@ -103,13 +105,14 @@ def mask_apply(mask, depth=None, color_a=None, color_b=None):
     return tuple(dst)
 
 
-def frame_metrics(render_color, render_depth, gt_color, mask, gt_depth=None):
+def frame_metrics(render_color, render_depth, gt_color, mask, gt_depth=None, lpips=None):
     """What eval_kf_imgs computes for one frame (eval_render.py:59-89).  render_color, gt_color [H,W,3], render_depth
     [H,W], mask [H,W] bool, gt_depth [H,W] or None, all on the device; the inputs are not modified.
     -> dict of 0-dim f32 device tensors psnr, ms_ssim, masked_psnr, masked_ms_ssim, depth_l1 (only with gt_depth: the
     mean |render_depth - gt_depth| over the mask), the int32 [1] mask_count, and the masked maps depth [H,W] and
     color, gt_color [H,W,3] (0 outside the mask).  masked_ms_ssim is, as in the reference, the full-frame MS-SSIM of
-    the two masked images, not a mean over the mask"""
+    the two masked images, not a mean over the mask.  lpips: an lpips.Lpips adds lpips and masked_lpips (eval_render.py:64-65,
+    :85-86), the latter likewise of the two masked images; None leaves both out and launches nothing more"""
     render_color, gt_color = _pair(render_color, gt_color)
     _hwc(render_color, "render_color")
     L.need_cuda(render_depth, mask, gt_depth)
@@ -126,5 +129,8 @@ def frame_metrics(render_color, render_depth, gt_color, mask, gt_depth=None):
     out["masked_ms_ssim"] = ms_ssim(m_gt, m_color)
     if gt_d is not None:
         out["depth_l1"] = sums[2]
+    if lpips is not None:
+        out["lpips"] = lpips(gt_color, render_color)
+        out["masked_lpips"] = lpips(m_gt, m_color)
     out.update(mask_count=count, depth=m_depth, color=m_color, gt_color=m_gt)
     return out

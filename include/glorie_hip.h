@@ -921,6 +921,29 @@ int glorie_frame_reduce(const float* color_a, const float* color_b, int H, int W
  * the input holds there); each output is written only when not NULL; the inputs are not modified.  One launch. */
 int glorie_mask_apply(const unsigned char* mask, int H, int W, const float* depth, const float* color_a,
                       const float* color_b, float* depth_out, float* color_a_out, float* color_b_out, void* stream);
+/* LPIPS of two images   reference: src/utils/eval_render.py:27-28, :64-65, :85-86
+ * (torchmetrics' LearnedPerceptualImagePatchSimilarity(net_type='alex', normalize=True): _LPIPS version 0.1, eval mode)
+ * x, y f32 [H,W,3] (or [3,H,W] with channels_first): clamp to [0,1], 2 v - 1, (v - shift) / scale, AlexNet's features
+ * tapped after each of the five ReLUs, per pixel f / sqrt(1e-8 + sum_c f^2) of both images, the lin-weighted squared
+ * difference, the mean over the pixels, the sum over the taps.  f32 convolutions on the exact-f32 MFMA (a k-ordered fmaf
+ * chain per 32 k, the chunks added in order), both images in one launch per layer (identical images give bit-identical
+ * features); the score in fp64 from per-workgroup partials added in a fixed order (no atomics: bitwise repeatable).
+ * weights: glorie_lpips_weight_floats() floats, 16-byte aligned: per layer the convolution weight as [kpad][Co] with row
+ * k = (ky ks + kx) Ci + c and zero rows up to kpad = 364, 1600, 1728, 3456, 2304; then the five biases [Co]; then the
+ * five lin weights [Co]; Co = 64, 192, 384, 256, 256.
+ * out f32 [6]: out[0] the LPIPS, out[1 + l] the mean of tap l.  features (NULL = kept in the workspace): 16-byte aligned,
+ * receives the five ReLU maps one after the other, map l as [2, h_l, w_l, Co_l] (image x, then y) with the sizes of
+ * glorie_lpips_shapes (hw HOST int [10] = h_0, w_0, .. h_4, w_4; no device work).
+ * flags: GLORIE_LPIPS_FOLD_POOLS takes the two max-pools inside the staging of the convolutions behind them (7 launches)
+ * instead of launches of their own (9); the results are bitwise the same.
+ * H or W below 31 (the last taps would be empty) or above 16384: GLORIE_EINVAL, and the workspace query returns 0.
+ * workspace: glorie_lpips_workspace(H, W) bytes, 16-byte aligned.  No allocation, no host synchronisation. */
+#define GLORIE_LPIPS_FOLD_POOLS 1
+size_t glorie_lpips_weight_floats(void);
+int glorie_lpips_shapes(int H, int W, int* hw);
+size_t glorie_lpips_workspace(int H, int W);
+int glorie_lpips(const float* x, const float* y, int H, int W, int channels_first, const float* weights, void* workspace,
+                 float* out, float* features, int flags, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* TSDF fusion and mesh extraction                                                       */
