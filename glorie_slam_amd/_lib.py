@@ -45,6 +45,10 @@ SIGNATURES = {
                                          _c_int, _c_int, _c_int, _c_int, _vp]),
     "glorie_conv_upsample": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp]),
     "glorie_conv_stencil": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, ctypes.c_float, _vp, _vp, _c_int, _c_int, _c_int, _vp]),
+    "glorie_heads_finish": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_f, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _c_int, _vp,
+                                     _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
+    "glorie_eta_finish": (_c_int, [_vp, _c_int, _vp, _vp, _c_f, _vp, _vp, _vp, _vp, _c_f, _vp, _c_int, _c_int, _c_int, _c_int,
+                                   _c_int, _vp]),
     "glorie_conv_igemm": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp,
                                    _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _c_int, _vp, _c_int, _vp,
                                    _c_int, _c_int, _c_int, _vp]),

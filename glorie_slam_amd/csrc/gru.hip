@@ -183,16 +183,17 @@ __global__ __launch_bounds__(256) void gru_gate_q_kernel(const _Float16* __restr
 // 256 candidates at a time and in ascending order (ballot + prefix count), then every thread walks that
 // short list: fixed summation order, no atomics, no zero fill, and no O(N) scan per thread on graphs with
 // thousands of edges.  grid (HW*16/256, G).
-__global__ __launch_bounds__(256) void segment_mean_kernel(const _Float16* __restrict__ x, int xs,
-                                                           const float* __restrict__ bias, int relu,
-                                                           const int64_t* __restrict__ ix, int N,
-                                                           _Float16* __restrict__ out, int os, int HW) {
+// (bx, g): the block's coordinates in that grid - glorie_heads_finish appends the same blocks to a 1-D grid
+__device__ __forceinline__ void segment_mean_body(int bx, int g, const _Float16* __restrict__ x, int xs,
+                                                  const float* __restrict__ bias, int relu,
+                                                  const int64_t* __restrict__ ix, int N,
+                                                  _Float16* __restrict__ out, int os, int HW) {
   __shared__ int elist[256];
   __shared__ int wcnt[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int idx = blockIdx.x * 256 + tid;
+  const int idx = bx * 256 + tid;
   const bool live = idx < HW * 16;
-  const int p = idx >> 4, c = (idx & 15) * 8, g = blockIdx.y;
+  const int p = idx >> 4, c = (idx & 15) * 8;
   float b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (bias) {
 #pragma unroll
@@ -234,6 +235,13 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(const _Float16* __res
 #pragma unroll
   for (int k = 0; k < 8; ++k) o[k] = (_Float16)(acc[k] * inv);
   *reinterpret_cast<h8*>(out + ((long)g * HW + p) * os + c) = o;
+}
+
+__global__ __launch_bounds__(256) void segment_mean_kernel(const _Float16* __restrict__ x, int xs,
+                                                           const float* __restrict__ bias, int relu,
+                                                           const int64_t* __restrict__ ix, int N,
+                                                           _Float16* __restrict__ out, int os, int HW) {
+  segment_mean_body(blockIdx.x, blockIdx.y, x, xs, bias, relu, ix, N, out, os, HW);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -305,13 +313,15 @@ __device__ __forceinline__ float softplusf_(float x) { return x > 20.0f ? x : lo
 
 // PLANAR: taps = [groups*ncols][P] (written by glorie_conv_igemm_heads; a wave reads 64 consecutive pixels of one tap
 // plane), else rows [P][groups*ncols] (conv_taps_kernel)
+// idx: the element of the [groups][P][K] result.  target (glorie_heads_finish): the thread that holds an element of group 0
+// (delta) also stores target = coords1 + delta, the sum of glorie_update_bookkeeping (flat index p*K + j, no contraction)
 template <bool PLANAR>
-__global__ __launch_bounds__(256) void conv_stencil_kernel(const float* __restrict__ taps, int ncols,
-                                                           int tstride, const float* __restrict__ bias,
-                                                           int K, int groups, int act_packed, float scale,
-                                                           float* __restrict__ out, long P, int H, int W,
-                                                           float* __restrict__ out_last = nullptr) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void conv_stencil_body(long idx, const float* __restrict__ taps, int ncols,
+                                                  int tstride, const float* __restrict__ bias,
+                                                  int K, int groups, int act_packed, float scale,
+                                                  float* __restrict__ out, long P, int H, int W,
+                                                  float* __restrict__ out_last, const float* __restrict__ coords1,
+                                                  float* __restrict__ target) {
   if (idx >= P * K * groups) return;
   const int gk = PLANAR ? (int)(idx / P) : (int)(idx % (K * groups));
   const long p = PLANAR ? idx - (long)gk * P : idx / (K * groups);
@@ -329,9 +339,116 @@ __global__ __launch_bounds__(256) void conv_stencil_kernel(const float* __restri
   if (act == ACT_RELU) acc = fmaxf(acc, 0.0f);
   else if (act == ACT_SIGMOID) acc = sigmoidf_(acc);
   else if (act == ACT_SOFTPLUS) acc = softplusf_(acc);
+  const float v = acc * scale;
   // out_last: the last group goes to a tensor of its own ([P][K]; e.g. the confidence weights straight into the caller's buffer)
-  if (out_last && grp == groups - 1) out_last[(size_t)p * K + j] = acc * scale;
-  else out[((size_t)grp * P + p) * K + j] = acc * scale;
+  if (out_last && grp == groups - 1) out_last[(size_t)p * K + j] = v;
+  else out[((size_t)grp * P + p) * K + j] = v;
+  if (target && grp == 0) {
+#pragma clang fp contract(off)
+    target[(size_t)p * K + j] = coords1[(size_t)p * K + j] + v;
+  }
+}
+
+template <bool PLANAR>
+__global__ __launch_bounds__(256) void conv_stencil_kernel(const float* __restrict__ taps, int ncols,
+                                                           int tstride, const float* __restrict__ bias,
+                                                           int K, int groups, int act_packed, float scale,
+                                                           float* __restrict__ out, long P, int H, int W,
+                                                           float* __restrict__ out_last = nullptr) {
+  conv_stencil_body<PLANAR>((long)blockIdx.x * 256 + threadIdx.x, taps, ncols, tstride, bias, K, groups, act_packed, scale,
+                            out, P, H, W, out_last, nullptr, nullptr);
+}
+
+// One launch behind glorie_conv_igemm_heads: the blocks [0, nb_stencil) are the grid of conv_stencil_kernel<true> (delta and
+// weight from the tap planes, + target = coords1 + delta), the rest is the grid (nbx, G) of segment_mean_kernel, row-major in
+// g.  The two jobs read different outputs of the heads launch and write different tensors; side by side they fill the chip
+// that either leaves half empty.
+__global__ __launch_bounds__(256) void heads_finish_kernel(const float* __restrict__ taps, int ncols, int tstride,
+                                                           const float* __restrict__ bias, int K, int groups,
+                                                           int act_packed, float scale, float* __restrict__ out, long P,
+                                                           int H, int W, float* __restrict__ out_last,
+                                                           const float* __restrict__ coords1, float* __restrict__ target,
+                                                           unsigned nb_stencil, const _Float16* __restrict__ x, int xs,
+                                                           const float* __restrict__ mbias, int relu,
+                                                           const int64_t* __restrict__ ix, int N,
+                                                           _Float16* __restrict__ agg, int os, int nbx) {
+  if (blockIdx.x < nb_stencil) {
+    conv_stencil_body<true>((long)blockIdx.x * 256 + threadIdx.x, taps, ncols, tstride, bias, K, groups, act_packed, scale,
+                            out, P, H, W, out_last, coords1, target);
+  } else {
+    const int b = (int)(blockIdx.x - nb_stencil);
+    segment_mean_body(b % nbx, b / nbx, x, xs, mbias, relu, ix, N, agg, os, H * W);
+  }
+}
+
+// The eta head of GraphAgg (droid_net.py:42-44: 3x3 convolution 128 -> 1, softplus, * scale) on G maps, with the rest of
+// glorie_update_bookkeeping, in one launch.  A workgroup owns R whole rows of one map: it forms the nine tap values of these
+// rows and of one halo row above and below (rows of the map only) with the MFMA sequence of conv_taps_kernel<1> - a row of
+// an MFMA result depends on that row's operands alone, so the tiling does not change a tap - keeps them in LDS as fp32
+// ([pixel][9]), and sums them in the order of conv_stencil_kernel<false>.  The thread that holds eta[i] stores it, its row
+// of the damping table and the BA's damping 0.2 * eta + ep; the launch's threads increment the ages (grid stride).
+__global__ __launch_bounds__(256) void eta_finish_kernel(const _Float16* __restrict__ x, int xs,
+                                                         const f16x8* __restrict__ wp, const float* __restrict__ bias,
+                                                         float scale, float* __restrict__ eta,
+                                                         const int64_t* __restrict__ frames,
+                                                         float* __restrict__ damping_table,
+                                                         float* __restrict__ damping_ba, float ep,
+                                                         int64_t* __restrict__ age, int n_edges, int G, int H, int W,
+                                                         int R, int nrb) {
+  extern __shared__ float tapl[];                 // [min(R + 2, H) * W][9]
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (age)
+    for (long i = (long)blockIdx.x * 256 + tid; i < n_edges; i += (long)gridDim.x * 256) age[i] += 1;
+  if (blockIdx.x >= (unsigned)(G * nrb)) return;  // the whole workgroup (a launch with ages only: G = 0)
+  const int g = blockIdx.x / nrb, r0 = (blockIdx.x - g * nrb) * R;
+  const int r1 = min(r0 + R, H), ra = max(r0 - 1, 0), rb = min(r1 + 1, H);
+  const int npx = (rb - ra) * W;
+  const long HW = (long)H * W, base = (long)g * HW + (long)ra * W;
+  const int col = lane & 15, kg = lane >> 4;
+  f16x8 bfrag[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) bfrag[kk] = wp[kk * 64 + lane];
+  const int ntiles = (npx + 15) / 16;
+  for (int tile = wv; tile < ntiles; tile += 4) {
+    const int p0 = tile * 16;
+    const int pa = min(p0 + col, npx - 1);
+    const f16x8* src = reinterpret_cast<const f16x8*>(x + (base + pa) * xs + kg * 8);
+    f16x8 afrag[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) afrag[kk] = src[kk * 4];
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(afrag[kk], bfrag[kk], acc, 0, 0, 0);
+    if (col < 9) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int pr = p0 + kg * 4 + r;
+        if (pr < npx) tapl[pr * 9 + col] = acc[r];
+      }
+    }
+  }
+  __syncthreads();
+  const int nown = (r1 - r0) * W;
+  for (int q = tid; q < nown; q += 256) {
+    const int yl = q / W, xw = q - yl * W, yh = r0 + yl;
+    float acc = bias ? bias[0] : 0.0f;
+#pragma unroll
+    for (int d = 0; d < 9; ++d) {
+      const int dy = d / 3 - 1, dx = d % 3 - 1;
+      if ((unsigned)(yh + dy) < (unsigned)H && (unsigned)(xw + dx) < (unsigned)W)
+        acc += tapl[((yh + dy - ra) * W + xw + dx) * 9 + d];
+    }
+    acc = softplusf_(acc);
+    const float e = acc * scale;
+    const long qm = (long)yh * W + xw, i = (long)g * HW + qm;
+    eta[i] = e;
+    {
+#pragma clang fp contract(off)
+      damping_table[(size_t)frames[g] * HW + qm] = e;
+      const float m = e * 0.2f;
+      damping_ba[i] = m + ep;
+    }
+  }
 }
 
 }  // namespace glorie
@@ -550,5 +667,51 @@ extern "C" int glorie_conv_stencil(const float* taps, const float* out_bias, int
   const long P = (long)N * H * W, total = P * K * groups;
   hipLaunchKernelGGL(conv_stencil_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      taps, 9 * K, 9 * K * groups, out_bias, K, groups, act_packed, scale, out, P, H, W, out_last);
+  return check_launch();
+}
+
+// glorie_conv_stencil (planar taps) and glorie_segment_mean as ONE launch, + target = coords1 + delta of
+// glorie_update_bookkeeping when coords1 / target are given
+extern "C" int glorie_heads_finish(const float* taps, const float* out_bias, int groups, int K, int act_packed, float scale,
+                                   float* out, float* out_last, const float* coords1, float* target, const void* x,
+                                   int x_stride, const float* bias, int relu, const int64_t* ix, void* agg, int o_stride,
+                                   int G, int N, int H, int W, void* stream) {
+  if (N < 0 || G < 0 || H <= 0 || W <= 0 || groups < 1 || groups > 4 || K < 1 || K > 3 || (x_stride & 7) || (o_stride & 7) ||
+      (coords1 == nullptr) != (target == nullptr))
+    return GLORIE_EINVAL;
+  if (N == 0 && G == 0) return GLORIE_OK;
+  if ((N > 0 && (!taps || !out)) || (G > 0 && (!agg || (N > 0 && (!x || !ix))))) return GLORIE_EINVAL;
+  const long HW = (long)H * W, P = (long)N * HW, total = P * K * groups;
+  const long nb_stencil = (total + 255) / 256, nbx = (HW * 16 + 255) / 256;
+  if (HW * 16 > 0x7fffffffL || nb_stencil + nbx * G > 0x7fffffffL) return GLORIE_EINVAL;
+  hipLaunchKernelGGL(heads_finish_kernel, dim3((unsigned)(nb_stencil + nbx * G)), dim3(256), 0, (hipStream_t)stream, taps,
+                     9 * K, 9 * K * groups, out_bias, K, groups, act_packed, scale, out, P, H, W, out_last, coords1, target,
+                     (unsigned)nb_stencil, reinterpret_cast<const _Float16*>(x), x_stride, bias, relu, ix, N,
+                     reinterpret_cast<_Float16*>(agg), o_stride, (int)nbx);
+  return check_launch();
+}
+
+// the eta head (glorie_conv3x3_small with one group, K = 1, softplus) and the eta half of glorie_update_bookkeeping as ONE
+// launch; rows_per_block = 0: chosen here.  GLORIE_EUNSUPPORTED (nothing launched): a row block does not fit 64 KB of LDS.
+extern "C" int glorie_eta_finish(const void* x, int x_stride, const void* w_packed, const float* out_bias, float scale,
+                                 float* eta, const int64_t* frames, float* damping_table, float* damping_ba, float ep,
+                                 int64_t* age, int n_edges, int rows_per_block, int G, int H, int W, void* stream) {
+  if (G < 0 || H <= 0 || W <= 0 || n_edges < 0 || rows_per_block < 0 || (x_stride & 7)) return GLORIE_EINVAL;
+  const int n_age = age ? n_edges : 0;
+  if (G == 0 && n_age == 0) return GLORIE_OK;
+  if (G > 0 && (!x || !w_packed || !eta || !frames || !damping_table || !damping_ba)) return GLORIE_EINVAL;
+  const long lds_row = (long)W * 9 * sizeof(float), lds_max = 64 * 1024;
+  // two rows per workgroup: 2x the input reads for the halo rows, and G * H / 2 workgroups (240 on 8 maps of 60 rows)
+  int R = rows_per_block ? rows_per_block : 2;
+  if (R > H) R = H;
+  if (!rows_per_block && min(R + 2, H) * lds_row > lds_max) R = 1;
+  const int lds_rows = min(R + 2, H);            // the block's rows and their halo, rows of the map only
+  if (lds_rows * lds_row > lds_max) return GLORIE_EUNSUPPORTED;
+  const int nrb = (H + R - 1) / R;
+  const long nb = max((long)G * nrb, 1L);
+  if (nb > 0x7fffffffL) return GLORIE_EINVAL;
+  hipLaunchKernelGGL(eta_finish_kernel, dim3((unsigned)nb), dim3(256), (size_t)(lds_rows * lds_row), (hipStream_t)stream,
+                     reinterpret_cast<const _Float16*>(x), x_stride, reinterpret_cast<const f16x8*>(w_packed), out_bias,
+                     scale, eta, frames, damping_table, damping_ba, ep, age, n_age, G, H, W, R, nrb);
   return check_launch();
 }

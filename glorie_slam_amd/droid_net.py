@@ -273,7 +273,9 @@ class FusedUpdate:
         (glorie_gru_glo_terms);
       * the 128 -> 2 / 128 -> 1 heads (delta[2], weight[2], agg.eta) are the tap-GEMM + stencil
         kernel glorie_conv3x3_small; GraphAgg's scatter_mean is glorie_segment_mean (fixed order);
-        the upmask logits stay channels-last for glorie_cvx_upsample_nhwc.
+        the upmask logits stay channels-last for glorie_cvx_upsample_nhwc.  For a caller that hands over its bookkeeping
+        (`book`, fuse_tail) the launches behind the heads' hidden convolution are three: glorie_heads_finish (stencil +
+        scatter_mean + target), agg.conv2, glorie_eta_finish (eta head + damping rows + ages).
 
     No convolution goes through MIOpen (flow_encoder[0] is glorie_flow_conv7).  Same call signature and
     return values as UpdateModule.forward (droid_net.py:106-139); delta, weight and eta come back
@@ -303,6 +305,9 @@ class FusedUpdate:
         self.fuse_heads = True    # tap GEMMs of the delta / weight heads inside the epilogue of their hidden convolution
         # flow encoder as one launch (glorie_flow_encoder); GLORIE_FLOW_FUSED=0 keeps its two launches
         self.fuse_flow = os.environ.get("GLORIE_FLOW_FUSED", "1") != "0"
+        # stencil + scatter_mean (+ target) as one launch, eta head + bookkeeping as one (glorie_heads_finish, glorie_eta_finish)
+        # for callers that pass `book`; GLORIE_TAIL_FUSED=0 keeps the six launches
+        self.fuse_tail = os.environ.get("GLORIE_TAIL_FUSED", "1") != "0"
         self.gate_events = None   # a list: (start, end) events of every z|r gate launch are appended (eager steps only)
         self.q_events = None      # the same for the q gate launch and for the heads' hidden convolution (bench.py)
         self.heads_events = None
@@ -375,6 +380,15 @@ class FusedUpdate:
         b, n, c, h, w = t.shape
         return t.reshape(b * n, c, h, w).half().contiguous(memory_format=torch.channels_last)
 
+    @staticmethod
+    def _agg_groups(ii, groups, dev):
+        """(ix int64 [N] contiguous, number of groups) of GraphAgg: the caller's, or unique(ii)"""
+        if groups is None:
+            uniq, ix = torch.unique(ii.to(dev), sorted=True, return_inverse=True)
+            return ix.contiguous(), uniq.shape[0]
+        ix, ngroups = groups
+        return ix.contiguous(), ngroups
+
     def _side_streams(self, dev):
         if self._streams is None or self._streams[0].device != dev:
             self._streams = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
@@ -416,12 +430,15 @@ class FusedUpdate:
 
     @torch.no_grad()
     def __call__(self, net, inp, corr, flow=None, ii=None, jj=None, groups=None, context=None, lazy_up=False,
-                 weight_out=None):
+                 weight_out=None, book=None):
         """corr: the looked-up correlation features [1,N,196,h,w], or a callable returning them (it is
         invoked on the caller's stream after the independent branches were forked).
         context (not in the reference): see precompute_shared_context; `inp` is then not read.
         lazy_up: return the upmask logits unevaluated (update_ops.LazyUpmask) for DepthVideo.upsample.
-        weight_out: float32 buffer of the confidence weights' size: they are written there (and returned as a view of it)."""
+        weight_out: float32 buffer of the confidence weights' size: they are written there (and returned as a view of it).
+        book: update_ops.TailBook - the caller's bookkeeping on delta and eta.  With fuse_tail, fuse_heads and ii it is done
+        by the operator's own launches (heads conv -> heads_finish -> agg.conv2 -> eta_finish), which sets book.done; else
+        it is left to the caller."""
         from . import update_ops as U
         self._sync()
         W = self.W
@@ -478,11 +495,13 @@ class FusedUpdate:
             else:
                 wn = U.conv_igemm(net0, None, W["w"], 1, 128, cl_map(128))
                 g = U.gru_glo_terms(wn, W["w_b"], net0, W["G"], W["G_b"])
+        joined = None
         if self.glo_stream and not self.parallel:
             # joined in front of the lookup: the branch is through by then (it started beside the 68 us flow encoder), and the
             # lookup keeps the chip to itself - with the join behind corr_encoder[2] its tail still overlapped the lookup:
             # step +0.4 %, lookup 48 -> 57 us
             main.wait_stream(side[1])
+            joined = side[1]
         # corr_encoder (droid_net.py:73-77): 1x1 as a transposed GEMM on the NCHW lookup output
         if hasattr(corr, "encode_into"):
             # volume-free lookup with corr_encoder[0] fused behind it (csrc/corr_otf.hip): the 196-channel map
@@ -509,7 +528,9 @@ class FusedUpdate:
                 U.bias_act(c1, W["ce1_b"], U.ACT_RELU)
         U.conv_igemm(c1, None, W["ce2"], 9, 128, hx[:, 128:256], terms=W["ce2_b"], act=U.ACT_RELU)
         for st in side:
-            if st is not main:
+            # a second join of the branch joined above (nothing was issued on it since) is not free: in the replayed step it
+            # left the chip idle for 6 us between this convolution and the z|r gates (profiles/tail_fused_step_trace.txt)
+            if st is not main and st is not joined:
                 main.wait_stream(st)
         # ConvGRU (gru.py:20-34)
         z, rnet = cl_map(128), cl_map(128)
@@ -540,6 +561,7 @@ class FusedUpdate:
             U.conv_igemm(net0, hx, W["zr"], 9, 256, z, epilogue=U.EPI_GRU_ZR, terms=g[:, 0:256], net=net0, out2=rnet)
             U.conv_igemm(rnet, hx, W["q"], 9, 128, new, epilogue=U.EPI_GRU_Q, terms=g[:, 256:384], net=net0, z=z)
         net_out = new.view(batch, num, 128, ht, wd)
+        tail = book is not None and self.fuse_tail and self.fuse_heads and ii is not None
         # heads (droid_net.py:85-93) + first conv of GraphAgg (droid_net.py:38,53)
         if self.fuse_heads:
             # the heads' hidden maps are consumed in the epilogue of their convolution (tap rows), only the GraphAgg third is stored
@@ -554,7 +576,12 @@ class FusedUpdate:
                 evh.append((h0, h1e))
             wo = weight_out if (weight_out is not None and weight_out.is_cuda and weight_out.dtype == torch.float32
                                 and weight_out.is_contiguous() and weight_out.numel() == n * ht * wd * 2) else None
-            dw = U.conv_stencil(rows, W["h2_b"], n, ht, wd, 2, 2, (U.ACT_NONE, U.ACT_SIGMOID), out_last=wo)
+            if tail:
+                ix, ngroups = self._agg_groups(ii, groups, dev)
+                dw, agg = U.heads_finish(rows, W["h2_b"], n, ht, wd, 2, 2, (U.ACT_NONE, U.ACT_SIGMOID), agg_in, ix, ngroups,
+                                         out_last=wo, coords1=book.coords1, target=book.target)
+            else:
+                dw = U.conv_stencil(rows, W["h2_b"], n, ht, wd, 2, 2, (U.ACT_NONE, U.ACT_SIGMOID), out_last=wo)
         else:
             h1 = U.conv_igemm(new, None, W["h1"], 9, 384, cl_map(384), terms=W["h1_b"], act=U.ACT_RELU)
             dw = U.conv3x3_small(h1, W["h2"], W["h2_b"], 2, (U.ACT_NONE, U.ACT_SIGMOID))
@@ -565,16 +592,28 @@ class FusedUpdate:
         if ii is None:
             return net_out, delta, weight
         # GraphAgg (droid_net.py:50-66): mean over edges with the same source keyframe
-        if groups is None:
-            uniq, ix = torch.unique(ii.to(dev), sorted=True, return_inverse=True)
-            ngroups = uniq.shape[0]
-        else:
-            ix, ngroups = groups
-        agg = U.segment_mean(agg_in, ix.contiguous(), ngroups)
+        if not tail:
+            ix, ngroups = self._agg_groups(ii, groups, dev)
+            agg = U.segment_mean(agg_in, ix, ngroups)
         a2 = torch.empty((ngroups, 128, ht, wd), dtype=torch.float16, device=dev,
                          memory_format=torch.channels_last)
         U.conv_igemm(agg, None, W["a2"], 9, 128, a2, terms=W["a2_b"], act=U.ACT_RELU)
-        eta = U.conv3x3_small(a2, W["eta"], W["eta_b"], 1, (U.ACT_SOFTPLUS,), scale=0.01)
+        eta = None
+        if tail:
+            eta = U.eta_finish(a2, W["eta"], W["eta_b"], book.frames, book.damping_table, book.damping_ba, book.ep, book.age,
+                               scale=0.01, strict=False)
+        if eta is None:
+            eta = U.conv3x3_small(a2, W["eta"], W["eta_b"], 1, (U.ACT_SOFTPLUS,), scale=0.01)
+            if tail:
+                # a map too wide for eta_finish's row blocks: the eta half of the bookkeeping as its own launch (the target
+                # is written already)
+                L = U.L
+                L.check(L.load().glorie_update_bookkeeping(
+                    None, None, None, 0, L.ptr(eta), L.ptr(book.frames), L.ptr(book.damping_table), L.ptr(book.damping_ba),
+                    ngroups, hw, book.ep, L.ptr(book.age), int(book.age.numel()) if book.age is not None else 0,
+                    L.stream_ptr()), "glorie_update_bookkeeping")
+        if tail:
+            book.done = True
         if lazy_up:
             # the caller only hands the logits to DepthVideo.upsample: convolution + convex upsampling run there as one
             # launch (glorie_conv_upsample), the 576-channel map is never stored

@@ -442,16 +442,28 @@ class FactorGraph:
         else:
             lookup = lambda: self.corr(coords1)
         uniq = self._unique_ii()
+        book = None
         if self.fast_update is not None:
             # the lookup is handed over as a callable: FusedUpdate issues it behind the fork of its
             # independent branches (flow encoder, global context), which then overlap with it
             # the edges of one source keyframe share their context features (inp = video.inps[ii], add_factors):
             # the hoisted gate term is kept per keyframe and shared through the GraphAgg grouping
             ix, _ = self._groups()
+            # the bookkeeping below handed to the operator's last launches (FusedUpdate.fuse_tail): the conditions of
+            # `fused_book` that do not depend on the operator's outputs (those are float32 and contiguous by construction)
+            if (getattr(self.fast_update, "fuse_tail", False) and self.fast_update.fuse_heads and not use_inactive
+                    and not self.video.is_sharded() and coords1.is_cuda
+                    and self.target.shape == coords1.shape and self.target.dtype == torch.float32
+                    and self.target.is_contiguous() and coords1.is_contiguous() and coords1.dtype == torch.float32
+                    and self.damping.dtype == torch.float32 and self.damping.is_contiguous() and self.age.is_contiguous()):
+                from .update_ops import TailBook
+                book = TailBook(coords1, self.target, uniq, self.damping,
+                                torch.empty((uniq.shape[0], self.ht, self.wd), dtype=torch.float32, device=coords1.device),
+                                EP, self.age)
             self.net, delta, weight, damping, upmask = \
                 self.fast_update(self.net, self.inp, lookup, motn, self.ii, self.jj, self._groups(),
                                  context=(self.video.inps, uniq, ix) if self.share_context else None,
-                                 lazy_up=True, weight_out=self.weight)
+                                 lazy_up=True, weight_out=self.weight, book=book)
         else:
             corr = lookup()
             with torch.autocast("cuda", enabled=True):
@@ -470,7 +482,12 @@ class FactorGraph:
                       and self.damping.dtype == torch.float32 and self.damping.is_contiguous()
                       and damping.numel() == uniq.shape[0] * self.ht * self.wd and self.age.is_contiguous())
         damping_ba = None
-        if fused_book:
+        if book is not None and book.done:
+            # glorie_heads_finish wrote the target, glorie_eta_finish the damping rows, the BA's damping and the ages
+            assert fused_book, "the operator did the bookkeeping on tensors the bookkeeping launch would not take"
+            damping_ba = book.damping_ba
+            self._age_done = True
+        elif fused_book:
             from . import _lib as L
             damping_ba = torch.empty((uniq.shape[0], self.ht, self.wd), dtype=torch.float32, device=coords1.device)
             L.check(L.load().glorie_update_bookkeeping(

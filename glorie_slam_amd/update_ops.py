@@ -340,6 +340,85 @@ def conv_stencil(rows, out_bias, n, h, w, groups, K, acts, scale=1.0, out_last=N
     return out
 
 
+class TailBook:
+    """what FactorGraph's bookkeeping between the update operator and the BA needs (glorie_update_bookkeeping), handed to
+    FusedUpdate so that the operator's last launches do it: coords1 / target float32 [1,N,h,w,2] contiguous (target =
+    coords1 + delta), frames int64 [G], damping_table float32 [B,h,w] (rows `frames` receive eta), damping_ba float32
+    [G,h,w] (receives 0.2 * eta + ep), age int64 [n_edges] or None (incremented).  `done` is set by the operator when its
+    launches wrote all of it."""
+
+    def __init__(self, coords1, target, frames, damping_table, damping_ba, ep, age):
+        self.coords1, self.target, self.frames, self.damping_table = coords1, target, frames, damping_table
+        self.damping_ba, self.ep, self.age = damping_ba, float(ep), age
+        self.done = False
+
+
+def _f32c(t, numel, name):
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel:
+        raise RuntimeError(f"{name} must be a contiguous float32 CUDA tensor of {numel} elements")
+
+
+def heads_finish(rows, out_bias, n, h, w, groups, K, acts, x, ix, ngroups, scale=1.0, out_last=None, coords1=None,
+                 target=None):
+    """conv_stencil(rows, ..., out_last=out_last) and segment_mean(x, ix, ngroups) as one launch (glorie_heads_finish), same
+    bits; with coords1 / target (contiguous float32, n*h*w*K elements) also target = coords1 + out[0].
+    Returns (out float32 [groups, n, h, w, K], agg fp16 channels-last [ngroups, 128, h, w])"""
+    L.need_cuda(rows, x, ix)
+    if rows.dtype != torch.float32 or tuple(rows.shape) != (groups * 9 * K, n * h * w) or not rows.is_contiguous() \
+            or len(acts) != groups:
+        raise RuntimeError("heads_finish: bad tap planes")
+    if tuple(x.shape) != (n, 128, h, w) or ix.dtype != torch.int64 or ix.numel() != n or not ix.is_contiguous():
+        raise RuntimeError("heads_finish: x must be [N,128,h,w], ix int64 [N]")
+    if out_last is not None:
+        _f32c(out_last, n * h * w * K, "heads_finish: out_last")
+    if (coords1 is None) != (target is None):
+        raise RuntimeError("heads_finish: coords1 and target come together")
+    if coords1 is not None:
+        _f32c(coords1, n * h * w * K, "heads_finish: coords1")
+        _f32c(target, n * h * w * K, "heads_finish: target")
+    out = torch.empty((groups, n, h, w, K), dtype=torch.float32, device=rows.device)
+    agg = torch.empty((ngroups, 128, h, w), dtype=torch.float16, device=x.device, memory_format=torch.channels_last)
+    packed = 0
+    for gidx, a in enumerate(acts):
+        packed |= int(a) << (4 * gidx)
+    L.check(L.load().glorie_heads_finish(L.ptr(rows), L.ptr(out_bias), groups, K, packed, float(scale), L.ptr(out),
+                                         L.ptr(out_last), L.ptr(coords1), L.ptr(target), L.ptr(x), _rows(x, "x"), None, 0,
+                                         L.ptr(ix), L.ptr(agg), 128, ngroups, n, h, w, L.stream_ptr()),
+            "glorie_heads_finish")
+    return out, agg
+
+
+def eta_finish(x, w_packed, out_bias, frames, damping_table, damping_ba, ep, age=None, scale=1.0, rows_per_block=0,
+               strict=True):
+    """the eta head conv3x3_small(x, w_packed, out_bias, 1, (ACT_SOFTPLUS,), scale) on x [G,128,h,w] and the eta half of
+    glorie_update_bookkeeping as one launch (glorie_eta_finish), same bits: damping_table[frames] = eta, damping_ba =
+    0.2 * eta + ep, age += 1.  Returns eta float32 [1, G, h, w, 1]; None (nothing launched, strict=False only) when a
+    row block of the map does not fit the kernel's LDS."""
+    L.need_cuda(x, w_packed, frames, damping_table, damping_ba, age)
+    g, c, h, w = x.shape
+    if c != 128 or w_packed.dtype != torch.float16 or tuple(w_packed.shape) != (1, 1, 4, 64, 8) or not w_packed.is_contiguous():
+        raise RuntimeError("eta_finish: x must be [G,128,h,w], w_packed = pack_conv3x3_small of one [1,128,3,3] weight")
+    if frames.dtype != torch.int64 or frames.numel() != g or not frames.is_contiguous():
+        raise RuntimeError("eta_finish: frames must be a contiguous int64 [G]")
+    if damping_table.dtype != torch.float32 or not damping_table.is_contiguous() or damping_table.dim() < 2 \
+            or damping_table[0].numel() != h * w:
+        raise RuntimeError("eta_finish: damping_table must be contiguous float32 [B,h,w]")
+    _f32c(damping_ba, g * h * w, "eta_finish: damping_ba")
+    if age is not None and (age.dtype != torch.int64 or not age.is_contiguous()):
+        raise RuntimeError("eta_finish: age must be a contiguous int64 tensor")
+    if out_bias is not None and (out_bias.dtype != torch.float32 or out_bias.numel() != 1):
+        raise RuntimeError("eta_finish: out_bias must be float32 [1]")
+    eta = torch.empty((1, g, h, w, 1), dtype=torch.float32, device=x.device)
+    status = L.load().glorie_eta_finish(L.ptr(x), _rows(x, "x"), L.ptr(w_packed), L.ptr(out_bias), float(scale), L.ptr(eta),
+                                        L.ptr(frames), L.ptr(damping_table), L.ptr(damping_ba), float(ep), L.ptr(age),
+                                        int(age.numel()) if age is not None else 0, int(rows_per_block), g, h, w,
+                                        L.stream_ptr())
+    if status == -4 and not strict:            # GLORIE_EUNSUPPORTED
+        return None
+    L.check(status, "glorie_eta_finish")
+    return eta
+
+
 def pack_flow_conv7(weight):
     """flow_encoder[0] weight [128,4,7,7] -> fp16 [128][224], column ky*32 + kx*4 + c (kx = 7 zero)"""
     if tuple(weight.shape) != (128, 4, 7, 7):

@@ -322,6 +322,26 @@ int glorie_conv_upsample(const void* x, int x_stride, int c, const void* w_packe
  * out_last (may be NULL): the LAST group is written there ([N*H*W][K]) instead of into its slice of out. */
 int glorie_conv_stencil(const float* taps, const float* out_bias, int groups, int K, int act_packed, float scale,
                         float* out, float* out_last, int N, int H, int W, void* stream);
+/* glorie_conv_stencil and glorie_segment_mean (both read outputs of glorie_conv_igemm_heads, neither the other's) as ONE
+ * launch whose grid is the two grids one after the other: same arithmetic in the same order, same bits.  taps .. out_last
+ * and N, H, W as glorie_conv_stencil; x .. o_stride and G as glorie_segment_mean (N edges = N maps).  coords1 / target
+ * (both or neither, [N*H*W][K] floats): the thread that holds an element of group 0 also stores target = coords1 + out[0],
+ * the sum of glorie_update_bookkeeping (its own rounding, no contraction); out[0] itself is still written. */
+int glorie_heads_finish(const float* taps, const float* out_bias, int groups, int K, int act_packed, float scale,
+                        float* out, float* out_last, const float* coords1, float* target, const void* x, int x_stride,
+                        const float* bias, int relu, const int64_t* ix, void* agg, int o_stride, int G, int N, int H, int W,
+                        void* stream);
+/* The eta head of GraphAgg (droid_net.py:42-44) and the eta half of glorie_update_bookkeeping as ONE launch:
+ *   eta[g][q] = scale * softplus(out_bias[0] + conv3x3(x[g])[q])   (glorie_conv3x3_small with groups = 1, K = 1: the same
+ *   MFMA sequence per pixel and the same order of the 9-point sum, the taps kept in LDS: same bits, no tap workspace),
+ *   damping_table[frames[g]][q] = eta[g][q], damping_ba[g][q] = 0.2 * eta[g][q] + ep, age[0..n_edges) += 1 (age may be NULL).
+ * x: fp16 rows [G*H*W][128], x_stride halfs apart; w_packed: the B fragments of glorie_conv3x3_small for one group, K = 1.
+ * A workgroup owns rows_per_block whole rows of one map (0: chosen by the library) and recomputes one halo row on either
+ * side; rows of other maps are never read.  G = 0 with ages is a valid call.  GLORIE_EUNSUPPORTED (nothing launched) when
+ * min(rows_per_block + 2, H) rows of W * 9 floats exceed 64 KB of LDS. */
+int glorie_eta_finish(const void* x, int x_stride, const void* w_packed, const float* out_bias, float scale, float* eta,
+                      const int64_t* frames, float* damping_table, float* damping_ba, float ep, int64_t* age, int n_edges,
+                      int rows_per_block, int G, int H, int W, void* stream);
 
 /* flow_encoder[0] (droid_net.py:79-81): 7x7 convolution, zero padding 3, 4 -> 128 channels, + bias
  * + ReLU.  flow: float32 channels-last motion map [N*H*W][4]; out: fp16 rows of 128 channels,
