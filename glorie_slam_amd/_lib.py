@@ -101,6 +101,11 @@ SIGNATURES = {
     "glorie_composite": (_c_int, [_vp, _vp, _c_int, _c_int, _c_f, _vp, _vp, _vp, _vp, _vp]),
     "glorie_ray_samples": (_c_int, [_vp] * 5 + [_c_int, _c_int, _c_f, _c_f] + [_vp] * 6),
     "glorie_ray_samples_camera": (_c_int, [_vp, _c_int, ctypes.c_long] + [_vp] * 3 + [_c_int, _c_int, _c_f, _c_f] + [_vp] * 6),
+    "glorie_ray_samples_near": (_c_int, [_vp] * 3 + [_c_f] + [_vp] * 5 + [_c_int, _c_int, _c_f, _c_f, ctypes.c_double, _vp,
+                                         _c_int] + [_vp] * 7),
+    "glorie_ray_samples_near_camera": (_c_int, [_vp] * 3 + [_c_f, _vp, _c_int, ctypes.c_long] + [_vp] * 3
+                                       + [_c_int, _c_int, _c_f, _c_f, ctypes.c_double, _vp, _c_int] + [_vp] * 7),
+    "glorie_near_pcl_chunk": (_c_int, []),
     "glorie_proj_depth": (_c_int, [_vp, _vp, ctypes.c_long, _vp, _c_f, _c_f, _c_f, _c_f, _c_int, _c_int, _vp, _vp]),
     "glorie_ray_counts": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
     "glorie_render_train_workspace": (_sz, [ctypes.c_long]),

@@ -509,6 +509,163 @@ __global__ __launch_bounds__(256) void knn_query_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------
+// sample placement with an on-device march for rays without a depth prior
+// ------------------------------------------------------------------------------------
+// Any-hit ball test on the cell list: true iff some cloud point has dist2_exact(q, p) < r2 - the predicate `cnt > 0` of
+// knn_query_kernel at the cloud's fixed query radius, without a top-k list or a pending buffer.  The cell rows that meet the
+// ball's box are visited as knn_search visits them (one contiguous point range per (z, y) row, clipped in x to the ball,
+// bounds widened by the same 1e-3 cell / 0.1 % so that the fp32 cell assignment can never hide a point) and the walk
+// stops at the first hit.  A ball outside the grid box (or a NaN position) reads nothing.
+__device__ __forceinline__ bool ball_any_hit(const float4* __restrict__ sorted, const int* __restrict__ starts,
+                                             const KnnGrid& g, float qx, float qy, float qz, float r, float r2) {
+  if (g.npoints <= 0) return false;
+  const float slack = 1e-3f * g.cs;
+  const float reach = r + slack;
+  // cell index of a coordinate as a float clamped to [-1, n]: -1 / n are "outside", NaN becomes -1
+  auto cell_f = [&](float v, float o, int n) { return fminf(fmaxf(floorf((v - o) * g.inv_cs), -1.0f), (float)n); };
+  const int xa = (int)cell_f(qx - reach, g.ox, g.nx), xb = (int)cell_f(qx + reach, g.ox, g.nx);
+  const int ya = (int)cell_f(qy - reach, g.oy, g.ny), yb = (int)cell_f(qy + reach, g.oy, g.ny);
+  const int za = (int)cell_f(qz - reach, g.oz, g.nz), zb = (int)cell_f(qz + reach, g.oz, g.nz);
+  if (xb < 0 || yb < 0 || zb < 0 || xa >= g.nx || ya >= g.ny || za >= g.nz) return false;
+  // (the build clamps points beyond the last cell boundary into the last cell: so are the bounds)
+  const int x0 = max(xa, 0), x1 = min(xb, g.nx - 1);
+  const int y0 = max(ya, 0), y1 = min(yb, g.ny - 1);
+  const int z0 = max(za, 0), z1 = min(zb, g.nz - 1);
+  const float lim = 1.001f * r2;
+#pragma unroll 1
+  for (int z = z0; z <= z1; ++z) {
+    const float zlo = g.oz + z * g.cs;
+    const float bz = fmaxf(fmaxf(zlo - qz, qz - (zlo + g.cs)) - slack, 0.0f);
+#pragma unroll 1
+    for (int y = y0; y <= y1; ++y) {
+      const float ylo = g.oy + y * g.cs;
+      const float by = fmaxf(fmaxf(ylo - qy, qy - (ylo + g.cs)) - slack, 0.0f);
+      const float byz2 = by * by + bz * bz;
+      if (byz2 > lim) continue;
+      const float rx = sqrtf(fmaxf(lim - byz2, 0.0f)) + slack;
+      const int ca = max(x0, cell_coord(qx - rx, g.ox, g.inv_cs, g.nx));
+      const int cb = min(x1, cell_coord(qx + rx, g.ox, g.inv_cs, g.nx));
+      if (ca > cb) continue;
+      const int row = (z * g.ny + y) * g.nx;
+      const int b = starts[row + ca], e = starts[row + cb + 1];
+#pragma unroll 1
+      for (int t = b; t < e; t += 2) {
+        const float4 p0 = sorted[t], p1 = sorted[min(t + 1, e - 1)];
+        if (dist2_exact(qx, qy, qz, p0) < r2 || dist2_exact(qx, qy, qz, p1) < r2) return true;
+      }
+    }
+  }
+  return false;
+}
+
+constexpr int kNearChunk = 64;       // probes marched per step: one per lane of the wave that owns the ray
+constexpr int kNearMaxS = 32;        // samples per ray (the lanes of the ray write them)
+constexpr int kNearMaxProbes = 4096;
+
+// glorie_ray_samples_near / _camera: ONE WAVE PER RAY, four rays per workgroup.
+//   depth > 0: the arithmetic of ray_samples_kernel (csrc/render.hip) - same bits.
+//   depth <= 0 (or no depth array): the ray is marched.  Probe k of `n` sits at (float)(near + k * step),
+//   step = (far - near) / (n - 1) in float64, the last one at (float)far (numpy.linspace rounded to fp32); lane l of the
+//   wave tests probe base + l, the ballot is the occupancy of 64 consecutive probes and its two lowest bits are the first
+//   and the second occupied probe.  The march goes front to back in chunks of 64 and ends with the second hit, after at
+//   most ceil(n / 64) steps whatever `far` holds.  The S samples then span the float64 depths of the two probes (both
+//   found) or [near, far] (near_mask = 0), again as numpy.linspace does.
+// A whole wave takes every branch below together: r, d and the march state are wave-uniform.
+template <bool CAMERA>
+__global__ __launch_bounds__(256) void ray_samples_near_kernel(
+    const float4* __restrict__ sorted, const int* __restrict__ starts, const KnnGrid* __restrict__ gp, float radius_query,
+    const float* __restrict__ rays_o, const float* __restrict__ rays_d, const float* __restrict__ cam, int img_w,
+    long first_pixel, const float* __restrict__ depth, const float* __restrict__ radius, const float* __restrict__ t_lin,
+    int R, int S, float near_s, float far_s, double near, const float* __restrict__ far_ptr, int n,
+    float* __restrict__ z_vals, float* __restrict__ pts, float* __restrict__ views, float* __restrict__ radius_s,
+    uint8_t* __restrict__ near_mask, int* __restrict__ bracket) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  float o[3], dir[3];
+  if (CAMERA) {
+    // get_rays, as ray_samples_kernel<true> forms it (reciprocal focal lengths, element 2 of the row sum added before 1)
+    const long px = first_pixel + r;
+    const float fi = (float)(px % img_w), fj = (float)(px / img_w);
+    const float x = (fi - cam[14]) * cam[12];
+    const float y = -((fj - cam[15]) * cam[13]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float q0 = x * cam[k * 4 + 0], q1 = y * cam[k * 4 + 1], q2 = -1.0f * cam[k * 4 + 2];
+      float sum = q0 + q2;
+      sum = sum + q1;
+      dir[k] = sum;
+      o[k] = cam[k * 4 + 3];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { dir[k] = rays_d[(size_t)r * 3 + k]; o[k] = rays_o[(size_t)r * 3 + k]; }
+  }
+  const float d = depth ? depth[r] : 0.0f;
+  float z = 0.0f;
+  int first = -1, second = -1, ok = 1;
+  if (d > 0.0f) {
+    if (lane < S) {
+      const float t = t_lin[lane];
+      const float a = near_s * d, c = far_s * d;
+      const float omt = 1.0f - t;
+      const float p1 = a * omt, p2 = c * t;
+      z = p1 + p2;
+    }
+  } else {
+    const KnnGrid g = *gp;
+    const double far = (double)far_ptr[0];
+    const double step = (far - near) / (double)(n - 1);
+    auto probe = [&](int k) -> double {
+      const double m = (double)k * step;
+      return k == n - 1 ? far : near + m;
+    };
+    const float r2 = radius_query * radius_query;
+#pragma unroll 1
+    for (int base = 0; base < n; base += kNearChunk) {
+      const int k = base + lane;
+      bool occ = false;
+      if (k < n) {
+        const float zk = (float)probe(k);
+        const float mx = dir[0] * zk, my = dir[1] * zk, mz = dir[2] * zk;
+        occ = ball_any_hit(sorted, starts, g, o[0] + mx, o[1] + my, o[2] + mz, radius_query, r2);
+      }
+      unsigned long long hits = __builtin_amdgcn_ballot_w64(occ);
+      if (hits != 0ull && first < 0) {
+        first = base + (int)__builtin_ctzll(hits);
+        hits &= hits - 1ull;
+      }
+      if (hits != 0ull && first >= 0) second = base + (int)__builtin_ctzll(hits);
+      if (second >= 0) break;
+    }
+    ok = second >= 0 ? 1 : 0;
+    const double lo = ok ? probe(first) : near, hi = ok ? probe(second) : far;
+    if (lane < S) {
+      const double ds = (hi - lo) / (double)(S > 1 ? S - 1 : 1);
+      const double m = (double)lane * ds;
+      z = (S > 1 && lane == S - 1) ? (float)hi : (float)(lo + m);
+    }
+  }
+  if (lane == 0) {
+    near_mask[r] = (uint8_t)ok;
+    bracket[(size_t)r * 2 + 0] = first;
+    bracket[(size_t)r * 2 + 1] = second;
+  }
+  if (lane < S) {
+    const size_t idx = (size_t)r * S + lane;
+    z_vals[idx] = z;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float m = dir[k] * z;
+      pts[idx * 3 + k] = o[k] + m;
+      views[idx * 3 + k] = dir[k];
+    }
+    if (radius_s) radius_s[idx] = radius[r];
+  }
+}
+
 }  // namespace glorie
 
 using namespace glorie;
@@ -611,3 +768,47 @@ extern "C" int glorie_knn_query_weights(const float* sorted_pos, const int* cell
                           image_w > 0 ? samples_per_ray : 1, image_w, stream, weights, has, min_nn, expo_weighting,
                           ball_only);
 }
+
+template <bool CAMERA>
+static int ray_samples_near_launch(const float* sorted_pos, const int* cell_start, const void* grid, float radius_query,
+                                   const float* rays_o, const float* rays_d, const float* cam, int image_w, long first_pixel,
+                                   const float* depth, const float* radius, const float* t_lin, int R, int S, float near_s,
+                                   float far_s, double near, const float* far, int intervals, float* z_vals, float* pts,
+                                   float* views, float* radius_s, uint8_t* near_mask, int* bracket, void* stream) {
+  if (R < 0 || S < 1 || intervals < 2 || intervals > kNearMaxProbes || !(radius_query > 0.0f)) return GLORIE_EINVAL;
+  if (S > kNearMaxS) return GLORIE_EUNSUPPORTED;
+  if (R == 0) return GLORIE_OK;
+  if (!sorted_pos || !cell_start || !grid || !far || !t_lin || !z_vals || !pts || !views || !near_mask || !bracket)
+    return GLORIE_EINVAL;
+  if ((radius == nullptr) != (radius_s == nullptr)) return GLORIE_EINVAL;
+  hipLaunchKernelGGL(ray_samples_near_kernel<CAMERA>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const float4*>(sorted_pos), cell_start, reinterpret_cast<const KnnGrid*>(grid),
+                     radius_query, rays_o, rays_d, cam, image_w, first_pixel, depth, radius, t_lin, R, S, near_s, far_s, near,
+                     far, intervals, z_vals, pts, views, radius_s, near_mask, bracket);
+  return check_launch();
+}
+
+extern "C" int glorie_ray_samples_near(const float* sorted_pos, const int* cell_start, const void* grid, float radius_query,
+                                       const float* rays_o, const float* rays_d, const float* depth, const float* radius,
+                                       const float* t_lin, int R, int S, float near_s, float far_s, double near,
+                                       const float* far, int intervals, float* z_vals, float* pts, float* views,
+                                       float* radius_s, uint8_t* near_mask, int* bracket, void* stream) {
+  if (R > 0 && (!rays_o || !rays_d)) return GLORIE_EINVAL;
+  return ray_samples_near_launch<false>(sorted_pos, cell_start, grid, radius_query, rays_o, rays_d, nullptr, 1, 0L, depth,
+                                        radius, t_lin, R, S, near_s, far_s, near, far, intervals, z_vals, pts, views,
+                                        radius_s, near_mask, bracket, stream);
+}
+
+extern "C" int glorie_ray_samples_near_camera(const float* sorted_pos, const int* cell_start, const void* grid,
+                                              float radius_query, const float* cam, int image_w, long first_pixel,
+                                              const float* depth, const float* radius, const float* t_lin, int R, int S,
+                                              float near_s, float far_s, double near, const float* far, int intervals,
+                                              float* z_vals, float* pts, float* views, float* radius_s, uint8_t* near_mask,
+                                              int* bracket, void* stream) {
+  if (image_w < 1 || first_pixel < 0 || (R > 0 && !cam)) return GLORIE_EINVAL;
+  return ray_samples_near_launch<true>(sorted_pos, cell_start, grid, radius_query, nullptr, nullptr, cam, image_w,
+                                       first_pixel, depth, radius, t_lin, R, S, near_s, far_s, near, far, intervals, z_vals,
+                                       pts, views, radius_s, near_mask, bracket, stream);
+}
+
+extern "C" int glorie_near_pcl_chunk(void) { return kNearChunk; }

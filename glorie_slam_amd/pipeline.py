@@ -67,9 +67,12 @@ class SequenceRunner:
                  mapping_window_size=None, keyframe_selection_method=None, frustum_feature_selection=None,
                  frustum_edge=None, color_grad_radius=None, pixels_based_on_color_grad=None, bind_npc_with_pose=None,
                  render_depth=None, use_mono_to_complete=None, mapping_schedule=False, mapping_vis=None,
-                 save_rendered_image=None):
+                 save_rendered_image=None, near_pcl_path="host"):
         self.net, self.video, self.cfg = net, video, cfg
         self.npc, self.decoders, self.renderer = npc, decoders, renderer
+        # rays without a depth prior (Renderer.near_pcl_path): "device" keeps the renders of evaluate(), of the contact
+        # sheets and of final_refine on the HIP path when a frame's depth has holes; "host" is the reference's route
+        renderer.near_pcl_path = near_pcl_path              # (anything else is a ValueError)
         dev = cfg["device"]
         self.device = dev
         self.filter = MotionFilter(net, video, cfg, thresh=cfg["tracking"].get("motion_filter", {}).get("thresh", 0.0),
@@ -975,6 +978,15 @@ class SequenceRunner:
         masked forms, depth L1 with gt_depth_fn; the masked maps and the metrics file under `output`).  Not part of run()"""
         from .eval_render import eval_kf_imgs
         return eval_kf_imgs(self, output=output, gt_depth_fn=gt_depth_fn, **kwargs)
+
+    def render_view(self, c2w, **kwargs):
+        """the map seen from the pose c2w [4,4], which need not be a keyframe's (Renderer.render_view: no depth prior, every
+        ray marched on the device); kwargs: stage, far, intervals, dynamic_r_query.  -> depth, uncertainty, color [H,W,3],
+        valid_ray_mask, valid_ray_counts as render_img returns them.  Not part of run()"""
+        npc = self.npc
+        c2w = torch.as_tensor(c2w, dtype=torch.float32).to(self.device)
+        return self.renderer.render_view(npc, self.decoders, c2w, self.device, npc_geo_feats=npc.get_geo_feats(),
+                                         npc_col_feats=npc.get_col_feats(), cloud_pos=npc.cloud_pos(), **kwargs)
 
     # ---- generate_mesh.py:55-123 ----------------------------------------------------------------------------------------
     def mesh(self, output=None, mesh_name_suffix="kf", scene="scene", **kwargs):

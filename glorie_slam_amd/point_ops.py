@@ -208,6 +208,83 @@ def ray_samples_camera(cam, image_w, first_pixel, depth, radius, S, near_s, far_
     return z, pts, views, rs, nz
 
 
+NEAR_PCL_MAX_SAMPLES = 32        # samples per ray glorie_ray_samples_near places (the lanes of the ray's wave)
+NEAR_PCL_MAX_PROBES = 4096
+
+
+def near_pcl_chunk():
+    """probes glorie_ray_samples_near marches per step (a bracket may span two chunks)"""
+    return int(L.load().glorie_near_pcl_chunk())
+
+
+def _near_outputs(R, S, radius, dev):
+    z = torch.empty(R, S, device=dev)
+    pts = torch.empty(R * S, 3, device=dev)
+    views = torch.empty(R * S, 3, device=dev)
+    rs = torch.empty(R * S, device=dev) if radius is not None else None
+    near_mask = torch.empty(R, dtype=torch.bool, device=dev)
+    bracket = torch.empty(R, 2, dtype=torch.int32, device=dev)
+    return z, pts, views, rs, near_mask, bracket
+
+
+def _near_far(far, dev):
+    """the far end of the march as one device float (a tensor stays on the device: no host read)"""
+    if torch.is_tensor(far):
+        return far.detach().to(dev, torch.float32).reshape(-1)[:1].contiguous()
+    return torch.full((1,), float(far), dtype=torch.float32, device=dev)
+
+
+def ray_samples_near(index, radius_query, rays_o, rays_d, depth, radius, S, near_s, far_s, near, far, intervals=25):
+    """ray_samples with the probe march of NeuralPointCloud.sample_near_pcl (neural_point.py:315-375) inside the
+    launch: rays with depth > 0 get the bits of ray_samples, rays with depth <= 0 (all rays with depth=None) are
+    bracketed by the first two of `intervals` probes between `near` and `far` (a float or a one-element device tensor)
+    that have a cloud point of `index` (KnnIndex) inside `radius_query`.
+    -> z_vals [R,S], pts [R*S,3], views [R*S,3], radius per sample [R*S] (None without `radius`), near_mask [R] bool
+    (False: fewer than two occupied probes, samples span [near, far]), bracket [R,2] int32 (the two probes, -1: none)."""
+    L.need_cuda(rays_o, rays_d)
+    dev = rays_o.device
+    R = rays_o.shape[0]
+    f = lambda t: t.detach().reshape(-1).contiguous().float()
+    o, d = f(rays_o), f(rays_d)
+    g = f(depth) if depth is not None else None
+    r = f(radius) if radius is not None else None
+    if (g is not None and g.shape[0] != R) or (r is not None and r.shape[0] != R):
+        raise RuntimeError("ray_samples_near: depth / radius must have one entry per ray")
+    tl, fr = t_lin(dev, S), _near_far(far, dev)
+    z, pts, views, rs, near_mask, bracket = _near_outputs(R, int(S), r, dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().glorie_ray_samples_near(L.ptr(index.sorted_pos), L.ptr(index.cell_start), L.ptr(index.grid),
+                                                 float(radius_query), L.ptr(o), L.ptr(d), L.ptr(g), L.ptr(r), L.ptr(tl), R,
+                                                 int(S), float(near_s), float(far_s), float(near), L.ptr(fr), int(intervals),
+                                                 L.ptr(z), L.ptr(pts), L.ptr(views), L.ptr(rs), L.ptr(near_mask),
+                                                 L.ptr(bracket), L.stream_ptr()), "glorie_ray_samples_near")
+    return z, pts, views, rs, near_mask, bracket
+
+
+def ray_samples_near_camera(index, radius_query, cam, image_w, first_pixel, n_rays, depth, radius, S, near_s, far_s, near,
+                            far, intervals=25):
+    """ray_samples_near for n_rays consecutive row-major pixels of the view `cam` (camera_block) starting at first_pixel:
+    get_rays happens inside the kernel, as in ray_samples_camera"""
+    L.need_cuda(cam)
+    dev = cam.device
+    R = int(n_rays)
+    f = lambda t: t.detach().reshape(-1).contiguous().float()
+    g = f(depth) if depth is not None else None
+    r = f(radius) if radius is not None else None
+    if (g is not None and g.shape[0] != R) or (r is not None and r.shape[0] != R):
+        raise RuntimeError("ray_samples_near_camera: depth / radius must have one entry per ray")
+    tl, fr = t_lin(dev, S), _near_far(far, dev)
+    z, pts, views, rs, near_mask, bracket = _near_outputs(R, int(S), r, dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().glorie_ray_samples_near_camera(L.ptr(index.sorted_pos), L.ptr(index.cell_start), L.ptr(index.grid),
+                                                        float(radius_query), L.ptr(cam), int(image_w), int(first_pixel),
+                                                        L.ptr(g), L.ptr(r), L.ptr(tl), R, int(S), float(near_s), float(far_s),
+                                                        float(near), L.ptr(fr), int(intervals), L.ptr(z), L.ptr(pts),
+                                                        L.ptr(views), L.ptr(rs), L.ptr(near_mask), L.ptr(bracket),
+                                                        L.stream_ptr()), "glorie_ray_samples_near_camera")
+    return z, pts, views, rs, near_mask, bracket
+
+
 def ray_counts(has, S, min_samples=3):
     """decoder.py:202-204: has [R*S] (bool / uint8) -> counts [R] int64, valid [R] bool"""
     L.need_cuda(has)

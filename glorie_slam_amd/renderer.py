@@ -25,7 +25,21 @@ class Renderer(object):
         self.sigmoid_coefficient = r['sigmoid_coef']
         self.near_end = r['near_end']
         self.use_dynamic_radius = cfg['pointcloud']['use_dynamic_radius']
+        # rays without a depth prior (not in the reference): "host" = the batch leaves the HIP path for sample_near_pcl
+        # and the op-by-op decoders (the reference's route, bit for bit what it always returned); "device" = the probe
+        # march runs inside the sampling launch (point_ops.ray_samples_near) and the batch stays on the HIP path
+        self.near_pcl_path = "host"
         self.H, self.W, self.fx, self.fy, self.cx, self.cy = slam.H, slam.W, slam.fx, slam.fy, slam.cx, slam.cy
+
+    @property
+    def near_pcl_path(self):
+        return getattr(self, "_near_pcl_path", "host")
+
+    @near_pcl_path.setter
+    def near_pcl_path(self, path):
+        if path not in ("host", "device"):
+            raise ValueError(f"near_pcl_path must be 'host' or 'device', got {path!r}")
+        self._near_pcl_path = path
 
     def eval_points(self, p, decoders, npc, stage='color', device=None, npc_geo_feats=None,
                     npc_col_feats=None, is_tracker=False, cloud_pos=None, pts_views_d=None,
@@ -74,29 +88,60 @@ class Renderer(object):
                 z[~nz] = torch.linspace(self.near_end, torch.max(far), steps=S, device=device).repeat((~nz).sum(), 1)
         return z, near_mask, nz
 
+    def _near_on_device(self):
+        """rays without depth are marched by the sampling launch (near_pcl_path == "device" and a configuration that
+        launch covers; anything else takes the host route)"""
+        return (self.near_pcl_path == "device" and bool(self.sample_near_pcl)
+                and 1 <= self.N_surface <= point_ops.NEAR_PCL_MAX_SAMPLES)
+
+    def _near_far(self, gt_depth, device):
+        """the far end of the probe march as sample_z forms it, left on the device"""
+        if gt_depth is None:
+            return torch.full((1,), 10.0, dtype=torch.float32, device=device)
+        return torch.minimum(5 * gt_depth.mean(), torch.max(gt_depth * 1.2)).float().reshape(1)
+
     def _render_fast(self, npc, decoders, rays_d, rays_o, stage, gt_depth, npc_geo_feats, npc_col_feats,
-                     cloud_pos, dynamic_r_query, image_w=None, camera=None, precise=False):
+                     cloud_pos, dynamic_r_query, image_w=None, camera=None, precise=False, n_rays=None, near=None):
         """Inference path of render_batch_ray for batches in which every ray has a depth prior: seven HIP
         launches (samples, KNN, IDW gather, three decoders, per-ray counts, compositing) and no torch glue.
-        Returns None when a ray has no depth (sample_near_pcl is needed: general path)."""
+        Returns None when a ray has no depth (sample_near_pcl is needed: general path).
+        With near_pcl_path == "device" the sampling launch marches the rays without depth itself: the same seven
+        launches, no zero-depth flag, no wait and never None; gt_depth may then be None (n_rays rays of `camera`);
+        near = (far, intervals) overrides the far end (a float or a device scalar) and the probe count (render_view)."""
         S = self.N_surface
-        R = gt_depth.shape[0]
         g = decoders.geo_decoder
         rad = dynamic_r_query if self.use_dynamic_radius else None
-        if camera is not None:
-            # render_img: the rays of this strip are formed inside the sampling kernel (get_rays fused, row R7)
-            cam, first_pixel = camera
-            z_vals, pts, views, rq, n_zero = point_ops.ray_samples_camera(cam, image_w, first_pixel, gt_depth, rad, S,
-                                                                          self.near_end_surface, self.far_end_surface)
+        near_mask = ev = None
+        if self._near_on_device():
+            far, intervals = near if near is not None else (None, None)
+            if far is None:
+                far = self._near_far(gt_depth, npc_geo_feats.device)
+            args = (gt_depth, rad, S, self.near_end_surface, self.far_end_surface, self.near_end, far, intervals or 25)
+            if camera is not None:
+                cam, first_pixel = camera
+                R = gt_depth.shape[0] if gt_depth is not None else int(n_rays)
+                z_vals, pts, views, rq, near_mask, _ = point_ops.ray_samples_near_camera(
+                    npc.index, npc.radius_query, cam, image_w, first_pixel, R, *args)
+            else:
+                R = rays_o.shape[0]
+                z_vals, pts, views, rq, near_mask, _ = point_ops.ray_samples_near(npc.index, npc.radius_query, rays_o, rays_d,
+                                                                                  *args)
         else:
-            z_vals, pts, views, rq, n_zero = point_ops.ray_samples(rays_o, rays_d, gt_depth, rad, S,
-                                                                   self.near_end_surface, self.far_end_surface)
-        # the zero-depth count travels to pinned host memory behind the sampling kernel; it is looked at after
-        # the rest of the batch has been enqueued, so the device never waits for the host
-        flag = self._pinned_flag()
-        flag.copy_(n_zero, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
+            R = gt_depth.shape[0]
+            if camera is not None:
+                # render_img: the rays of this strip are formed inside the sampling kernel (get_rays fused, row R7)
+                cam, first_pixel = camera
+                z_vals, pts, views, rq, n_zero = point_ops.ray_samples_camera(cam, image_w, first_pixel, gt_depth, rad, S,
+                                                                              self.near_end_surface, self.far_end_surface)
+            else:
+                z_vals, pts, views, rq, n_zero = point_ops.ray_samples(rays_o, rays_d, gt_depth, rad, S,
+                                                                       self.near_end_surface, self.far_end_surface)
+            # the zero-depth count travels to pinned host memory behind the sampling kernel; it is looked at after
+            # the rest of the batch has been enqueued, so the device never waits for the host
+            flag = self._pinned_flag()
+            flag.copy_(n_zero, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
         # neighbours + IDW weights + mask from ONE launch (the geometry kernel interpolates its feature itself: no [Q,32] round
         # trip).  The search is bounded by the query radius (per sample, or the cloud's fixed one): I / D are exact inside
         # the ball - the only slots with a non-zero weight - and unspecified beyond it (NeuralPointCloud.find_neighbors_faiss)
@@ -112,6 +157,8 @@ class Renderer(object):
         counts, valid = point_ops.ray_counts(has, S, 3)
         depth, var, rgb, _ = point_ops.composite(raw.view(R, S, 4), z_vals, self.sigmoid_coefficient,
                                                  return_weights=False)
+        if near_mask is not None:
+            return depth, var, rgb, valid & near_mask, counts
         ev.synchronize()
         if int(flag[0]) != 0:
             return None
@@ -163,8 +210,10 @@ class Renderer(object):
         self._flag_slot = 0
 
     def _fast_ok(self, decoders, probe, R, gt_depth, stage, npc_geo_feats, npc_col_feats, is_tracker, dynamic_r_query):
-        """the batch can take the all-HIP inference path (every ray must also have a depth prior: checked on the device)"""
-        return (gt_depth is not None and R > 0 and torch.numel(gt_depth) == R and stage in ('geometry', 'color')
+        """the batch can take the all-HIP inference path (every ray must also have a depth prior: checked on the device;
+        with near_pcl_path == "device" rays without one, or a batch without gt_depth, are accepted too)"""
+        depth_ok = (gt_depth is not None and torch.numel(gt_depth) == R) or (gt_depth is None and self._near_on_device())
+        return (depth_ok and R > 0 and stage in ('geometry', 'color')
                 and getattr(self, "use_fast_path", True)
                 and (dynamic_r_query is not None or not self.use_dynamic_radius)
                 and decoders._fused_ok(probe, npc_geo_feats, npc_col_feats, is_tracker, stage)
@@ -172,23 +221,26 @@ class Renderer(object):
 
     def render_batch_ray(self, npc, decoders, rays_d, rays_o, device, stage, gt_depth=None,
                          npc_geo_feats=None, npc_col_feats=None, is_tracker=False, cloud_pos=None,
-                         dynamic_r_query=None, image_w=None, defer_guard=False):
+                         dynamic_r_query=None, image_w=None, defer_guard=False, near=None):
         """Renderer.py:80-219 -> depth, uncertainty, color, valid_ray_mask, valid_ray_counts
         image_w (not in the reference): the rays are consecutive row-major pixels of an image of that width, starting
         at a row start - lets the neighbour search walk the image in patches; the result does not depend on it.
         defer_guard (not in the reference): do not read the decoders' range guard behind this batch (a host synchronisation:
         the device then idles while the next batch is enqueued, ~0.1 ms per batch) - the caller reads
         `decoders.range_guard(device).tripped()` once behind its last batch and, if it is set, renders again without this flag
-        (what render_img does for its strips)."""
+        (what render_img does for its strips).
+        near (not in the reference; near_pcl_path == "device" only): (far, intervals) of the probe march of the rays
+        without depth - the far end (a float or a one-element device tensor; None: as sample_z forms it) and the number
+        of probes (None: the reference's 25)."""
         S = self.N_surface
         R = rays_o.shape[0]
         if self._fast_ok(decoders, rays_o, R, gt_depth, stage, npc_geo_feats, npc_col_feats, is_tracker, dynamic_r_query):
             out = self._render_fast(npc, decoders, rays_d, rays_o, stage, gt_depth, npc_geo_feats,
-                                    npc_col_feats, cloud_pos, dynamic_r_query, image_w=image_w)
+                                    npc_col_feats, cloud_pos, dynamic_r_query, image_w=image_w, near=near)
             if out is not None and not defer_guard and decoders.range_guard(rays_o.device).tripped():
                 # an activation, feature or weight outside the fp16 range: the split kernels' result is void
                 out = self._render_fast(npc, decoders, rays_d, rays_o, stage, gt_depth, npc_geo_feats,
-                                        npc_col_feats, cloud_pos, dynamic_r_query, image_w=image_w, precise=True)
+                                        npc_col_feats, cloud_pos, dynamic_r_query, image_w=image_w, precise=True, near=near)
             if out is not None:
                 return out
         if (torch.is_grad_enabled() and gt_depth is not None and R > 0 and torch.numel(gt_depth) == R and not is_tracker
@@ -225,8 +277,9 @@ class Renderer(object):
 
     @torch.no_grad()
     def render_img(self, npc, decoders, c2w, device, stage, gt_depth=None, npc_geo_feats=None,
-                   npc_col_feats=None, dynamic_r_query=None, cloud_pos=None, _precise=False):
-        """Renderer.py:221-306"""
+                   npc_col_feats=None, dynamic_r_query=None, cloud_pos=None, _precise=False, _near=None):
+        """Renderer.py:221-306.  With near_pcl_path == "device" a strip with depth holes, or a frame without gt_depth, stays
+        on the camera-block path below like any other strip (_near: the (far, intervals) of render_view)."""
         H, W = self.H, self.W
         n_rays = H * W
         if self.use_dynamic_radius:
@@ -240,8 +293,9 @@ class Renderer(object):
         # strips in which every pixel has a depth prior never materialise their rays: get_rays (common.py:302-322) is
         # evaluated inside the sampling kernel (row R7 fused into R4); the ray tensors are only built if a strip needs
         # the general path
+        has_depth = gt.is_cuda if gt is not None else (self._near_on_device() and torch.device(device).type == "cuda")
         cam = point_ops.camera_block(c2w, self.fx, self.fy, self.cx, self.cy, device) \
-            if (image_w and gt is not None and gt.is_cuda and getattr(self, "fuse_get_rays", True)) else None
+            if (image_w and has_depth and getattr(self, "fuse_get_rays", True)) else None
         rays = None
         bad_any = False
         two = cam is not None and n_rays > bs and not torch.is_grad_enabled()
@@ -251,11 +305,11 @@ class Renderer(object):
             g_i = gt[i:i + bs] if gt is not None else None
             r_i = dynamic_r_query[i:i + bs] if self.use_dynamic_radius else None
             ret = None
-            if cam is not None and self._fast_ok(decoders, g_i, g_i.shape[0], g_i, stage, npc_geo_feats, npc_col_feats,
-                                                 False, r_i):
+            n_i = min(bs, n_rays - i)
+            if cam is not None and self._fast_ok(decoders, cam, n_i, g_i, stage, npc_geo_feats, npc_col_feats, False, r_i):
                 with torch.cuda.stream(self.batch_stream(k, device) if two else torch.cuda.current_stream(torch.device(device))):
                     ret = self._render_fast(npc, decoders, None, None, stage, g_i, npc_geo_feats, npc_col_feats, cloud_pos,
-                                            r_i, image_w=image_w, camera=(cam, i), precise=_precise)
+                                            r_i, image_w=image_w, camera=(cam, i), precise=_precise, n_rays=n_i, near=_near)
             if ret is None and two:
                 self.join_batches(device)              # the general path runs on the caller's stream
                 two = False
@@ -269,7 +323,7 @@ class Renderer(object):
                 ret = self.render_batch_ray(
                     npc, decoders, rays[1][i:i + bs], rays[0][i:i + bs], device, stage, gt_depth=g_i,
                     npc_geo_feats=npc_geo_feats, npc_col_feats=npc_col_feats, cloud_pos=cloud_pos,
-                    dynamic_r_query=r_i, image_w=image_w)
+                    dynamic_r_query=r_i, image_w=image_w, near=_near)
             for o, v in zip(outs, ret):
                 o.append(v)
         if two:
@@ -280,10 +334,48 @@ class Renderer(object):
             return self.render_img(npc, decoders, c2w, device, stage, gt_depth=gt_depth, npc_geo_feats=npc_geo_feats,
                                    npc_col_feats=npc_col_feats,
                                    dynamic_r_query=dynamic_r_query.reshape(H, W) if self.use_dynamic_radius else None,
-                                   cloud_pos=cloud_pos, _precise=True)
+                                   cloud_pos=cloud_pos, _precise=True, _near=_near)
         depth = torch.cat(outs[0]).double().reshape(H, W)
         unc = torch.cat(outs[1]).double().reshape(H, W)
         color = torch.cat(outs[2]).reshape(H, W, 3)
         vmask = torch.cat(outs[3]).double().reshape(H, W)
         vcount = torch.cat(outs[4]).double().reshape(H, W)
         return depth, unc, color, vmask, vcount
+
+    @torch.no_grad()
+    def render_view(self, npc, decoders, c2w, device, stage="color", far=10.0, intervals=None, dynamic_r_query=None,
+                    npc_geo_feats=None, npc_col_feats=None, cloud_pos=None):
+        """A novel view of the map (not in the reference): render_img from the pose c2w without any depth prior.  Every ray
+        is marched on the device (point_ops.ray_samples_near) whatever near_pcl_path says: `intervals` probes between
+        near_end and `far`, the samples between the first two probes that have a cloud point inside radius_query.
+        intervals=None: ceil((far - near_end) / radius_query) + 1 probes - a spacing of at most one ball radius, so the two
+        probes enclose the surface (the reference's 25 probes up to far = 6 stand 24 cm apart against a ball 16 cm across).
+        dynamic_r_query [H,W]: the per-pixel decoder radius when the cloud uses dynamic radii; None: the constant radius the
+        training rays carry without colour-gradient radii, 0.5 * (radius_add + radius_query).
+        -> what render_img returns; pixels whose ray met fewer than two occupied probes have valid_ray_mask == 0."""
+        import math
+        geo = npc.get_geo_feats() if npc_geo_feats is None else npc_geo_feats
+        col = npc.get_col_feats() if npc_col_feats is None else npc_col_feats
+        far = float(far)
+        if intervals is None:
+            intervals = int(math.ceil((far - self.near_end) / npc.radius_query)) + 1
+        intervals = int(intervals)
+        if not 2 <= intervals <= point_ops.NEAR_PCL_MAX_PROBES:
+            raise ValueError(f"render_view: intervals must lie in [2, {point_ops.NEAR_PCL_MAX_PROBES}], got {intervals}")
+        if self.use_dynamic_radius and dynamic_r_query is None:
+            dynamic_r_query = torch.full((self.H, self.W), 0.5 * (npc.radius_add + npc.radius_query), dtype=torch.float32,
+                                         device=device)
+        saved = self.near_pcl_path
+        self.near_pcl_path = "device"
+        try:
+            bs = self.ray_batch_size
+            whole_rows = bs >= 16 * self.W or bs % self.W == 0         # render_img's strips start at row starts
+            if not (self._near_on_device() and whole_rows and getattr(self, "fuse_get_rays", True) and self._fast_ok(
+                    decoders, geo, self.H * self.W, None, stage, geo, col, False, dynamic_r_query)):
+                raise RuntimeError("render_view: this configuration is not covered by the device march (it needs "
+                                   "rendering.sample_near_pcl, N_surface <= 32, the fused decoders and no autograd)")
+            far_t = torch.full((1,), far, dtype=torch.float32, device=device)
+            return self.render_img(npc, decoders, c2w, device, stage, gt_depth=None, npc_geo_feats=geo, npc_col_feats=col,
+                                   dynamic_r_query=dynamic_r_query, cloud_pos=cloud_pos, _near=(far_t, intervals))
+        finally:
+            self.near_pcl_path = saved

@@ -673,6 +673,35 @@ int glorie_ray_samples_camera(const float* cam, int image_w, long first_pixel, c
                               const float* t_lin, int R, int S, float near_s, float far_s, float* z_vals, float* pts,
                               float* views, float* radius_s, int* n_zero, void* stream);
 
+/* glorie_ray_samples with an on-device march for the rays without a depth prior (depth[r] <= 0, or every ray when depth
+ * is NULL): one launch places every sample of the batch, no count travels to the host.
+ *   reference: src/neural_point.py:315-375 (sample_near_pcl), src/utils/Renderer.py:127-174
+ * sorted_pos / cell_start / grid: the cell list of glorie_knn_build; radius_query: the cloud's fixed query radius r.
+ * Rays with depth > 0: the bits of glorie_ray_samples, near_mask = 1, bracket = (-1, -1).
+ * Marched rays: probe k of `intervals` (2 .. 4096) sits at depth (float)(near + k * step), step = (*far - near) /
+ * (intervals - 1) in double, the last one at (float)*far (numpy.linspace(near, far, intervals) rounded to fp32; *far is
+ * one device float), at position o + dir * z_k (product and sum rounded separately).  A probe is occupied iff a cloud
+ * point lies at a squared distance ((dx*dx + dy*dy) + dz*dz) < r*r from it - `neighbor_num > 0` of glorie_knn_query at
+ * that radius.  With two occupied probes, bracket = (first, second), near_mask = 1 and the S samples are
+ * numpy.linspace(lo, hi, S) of the two probes' double depths rounded to fp32; otherwise bracket = (first or -1, -1),
+ * near_mask = 0 and the samples are numpy.linspace(near, *far, S).  pts / views / radius_s as glorie_ray_samples.
+ * near_mask [R] uint8, bracket [R,2] int32.  S <= 32 (more: GLORIE_EUNSUPPORTED).  An empty cloud occupies no probe. */
+int glorie_ray_samples_near(const float* sorted_pos, const int* cell_start, const void* grid, float radius_query,
+                            const float* rays_o, const float* rays_d, const float* depth, const float* radius,
+                            const float* t_lin, int R, int S, float near_s, float far_s, double near, const float* far,
+                            int intervals, float* z_vals, float* pts, float* views, float* radius_s, uint8_t* near_mask,
+                            int* bracket, void* stream);
+
+/* glorie_ray_samples_near for R consecutive row-major pixels of the view `cam` (see glorie_ray_samples_camera) */
+int glorie_ray_samples_near_camera(const float* sorted_pos, const int* cell_start, const void* grid, float radius_query,
+                                   const float* cam, int image_w, long first_pixel, const float* depth,
+                                   const float* radius, const float* t_lin, int R, int S, float near_s, float far_s,
+                                   double near, const float* far, int intervals, float* z_vals, float* pts, float* views,
+                                   float* radius_s, uint8_t* near_mask, int* bracket, void* stream);
+
+/* number of probes glorie_ray_samples_near marches per step (a bracket may span two such chunks) */
+int glorie_near_pcl_chunk(void);
+
 /* proj_depth_map(c2w, npc, ...): z-buffer projection of a point set into a view
  *   reference: src/neural_point.py:446-506
  * points [n,3] world coordinates, mask [n] uint8 (NULL = all points), w2c = inverse of the camera-to-world
