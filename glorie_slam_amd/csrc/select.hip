@@ -127,8 +127,9 @@ overlap_count_kernel(const float* __restrict__ rays_o, const float* __restrict__
     const int r = e / n_samples, s = e - r * n_samples;
     const float d = depth[r];
     if (!(d > 0.f)) continue;                                   // get_samples(..., depth_filter=True)
-    // torch.linspace(0, 1, S): the first half from the start, the second half from the end
-    const float t = s < n_samples / 2 ? (float)s * step : 1.f - (float)(n_samples - 1 - s) * step;
+    // torch.linspace(0, 1, S): a single sample is the start; else the first half from the start, the rest from the end
+    const float t = n_samples == 1 ? 0.f
+                    : s < n_samples / 2 ? (float)s * step : 1.f - (float)(n_samples - 1 - s) * step;
     const float zs = (0.8f * d) * (1.f - t) + (d + 0.5f) * t;
     const Proj p = project(w.r, rays_o[3 * r] + rays_d[3 * r] * zs, rays_o[3 * r + 1] + rays_d[3 * r + 1] * zs,
                            rays_o[3 * r + 2] + rays_d[3 * r + 2] * zs, fx, fy, cx, cy, kProjEps);
