@@ -166,6 +166,14 @@ SIGNATURES = {
     "glorie_points_in_view": (_c_int, [_vp, _c_int, _vp] + [_c_f] * 4 + [_c_int, _c_int, _c_f, _vp, _vp]),
     "glorie_depth_l1_workspace": (_sz, [_c_int, _c_int]),
     "glorie_depth_l1_accumulate": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_int, _vp]),
+    "glorie_mesh_visibility": (_c_int, [_vp, _c_int, _vp, _c_int] + [_c_f] * 4 + [_c_int, _c_int, _c_f, _c_f, _c_int, _vp, _c_f,
+                                         _c_int, _c_int, _vp, _vp]),
+    "glorie_mesh_select_faces": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp]),
+    "glorie_mesh_compact_workspace": (_sz, [_c_int, _c_int]),
+    "glorie_mesh_compact_count": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, ctypes.POINTER(_c_int), _vp]),
+    "glorie_mesh_compact_emit": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    "glorie_mesh_components_workspace": (_sz, []),
+    "glorie_mesh_components": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "glorie_window_rays": (_c_int, [_vp] * 4 + [_c_int] * 5 + [_c_f] * 4 + [_vp, _vp, _c_f, _c_int] + [_vp] * 6),
     "glorie_valid_index_build": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
     "glorie_sample_window_rays": (_c_int, [_vp] * 4 + [_c_int] * 5 + [_c_f] * 4 + [_vp, _vp, _vp, _c_f, _c_int] + [_vp] * 8),

@@ -9,7 +9,7 @@ ratio and depth L1 of a reconstructed mesh against the ground-truth mesh.
   render_depth       the depth map of a mesh from a pinhole camera (the rasteriser that stands in for :166-217)
   sample_views       random cameras inside the ground truth's bound (:121-138, :171-187)
   calc_2d_metric     :141-227 depth L1 over random views
-  eval_recon         :229-248; writes metrics_recon.txt
+  eval_recon         :229-248; writes metrics_recon.txt; cull= cuts both meshes to given views first (cull_mesh.py)
 
 Device tensors throughout; numpy float64 on the host only for 3x3 and 4x4 algebra.  Cameras are OpenCV pinholes whose
 pixel (u, v) samples image coordinates (u, v) (tsdf.py), which is why cx = W / 2 - 0.5.
@@ -462,14 +462,38 @@ def _load(mesh, device):
     return mesh[0], mesh[1]
 
 
-def eval_recon(rec, gt, eval_2d=True, eval_3d=True, align=True, output=None, device="cuda", kwargs_3d=None, kwargs_2d=None):
+def _cull_pair(rec, gt, cull):
+    """both meshes cut to the same views (cull_mesh.py).  cull: {"c2ws", "K", "H", "W"} and the keywords of cull_mesh; with
+    method "occlusion" and no depths both are tested against the depth of the ground truth, rasterised once per view"""
+    from . import cull_mesh as C
+    cull = dict(cull)
+    c2ws, K, H, W = (cull.pop(k) for k in ("c2ws", "K", "H", "W"))
+    method, depths = cull.pop("method", "frustum"), cull.pop("depths", None)
+    rule, min_views = cull.pop("rule", "all"), cull.pop("min_views", 1)
+    if method not in ("frustum", "occlusion"):
+        raise ValueError(f"method must be 'frustum' or 'occlusion', got {method!r}")
+    (rec_v, rec_f), (gt_v, gt_f) = rec, gt
+    if method == "occlusion" and depths is None:
+        counts = C.self_occlusion_visibility(gt_v, gt_f, c2ws, K, H, W, test_vertices=[rec_v, gt_v], **cull)
+    else:
+        counts = [C.vertex_visibility(v, c2ws, K, H, W, depths=depths if method == "occlusion" else None, **cull)
+                  for v in (rec_v, gt_v)]
+    return tuple(C.compact_mesh(v, f, C.select_faces(f, c, min_views, rule)) for (v, f), c in zip((rec, gt), counts))
+
+
+def eval_recon(rec, gt, eval_2d=True, eval_3d=True, align=True, output=None, device="cuda", kwargs_3d=None, kwargs_2d=None,
+               cull=None):
     """rec, gt: (vertices, faces) device tensors or paths of PLYs in the layout generate_mesh.write_ply writes.  The ICP
-    alignment (align=True) is computed once and shared.  -> the merged dict of calc_3d_metric and calc_2d_metric; with
+    alignment (align=True) is computed once and shared.  cull: None, or a dict {"c2ws" [M,4,4] views in the ground truth's
+    frame, "K", "H", "W", "method", "depths", ..} (_cull_pair): the ground truth and the aligned reconstruction are cut to
+    those views before they are scored.  -> the merged dict of calc_3d_metric and calc_2d_metric; with
     `output` also output/metrics_recon.txt, one "name: value" line per entry"""
     rec, gt = _load(rec, device), _load(gt, device)
     rec_v, rec_f = _mesh(*rec)
     gt_v, gt_f = _mesh(*gt)
     rec_v, _ = _aligned(rec_v, gt_v, align)
+    if cull is not None:
+        (rec_v, rec_f), (gt_v, gt_f) = _cull_pair((rec_v, rec_f), (gt_v, gt_f), cull)
     result = {}
     if eval_3d:
         result.update(calc_3d_metric((rec_v, rec_f), (gt_v, gt_f), align=False, **(kwargs_3d or {})))

@@ -77,6 +77,26 @@ def fuse_frames(frames, intrinsics, device, scale=1.0, transform=None, voxel_len
     return vol.extract() + (vol,)
 
 
+def cull_and_clean(vertices, colors, faces, frames, intrinsics, scale=1.0, transform=None, cull=None, clean=None):
+    """the post-processing of a fused mesh (cull_mesh.py).  cull: a dict of cull_mesh keywords - the views are the poses of
+    `frames` placed as fuse_frames places them, and for method "occlusion" without depths of its own the depths are the
+    frames' depths times `scale`; clean: a dict of clean_mesh keywords.  None leaves the mesh as it is"""
+    if (cull is None and clean is None) or faces.shape[0] == 0:
+        return vertices, colors, faces
+    from . import cull_mesh as C
+    if cull is not None and frames:
+        cull = dict(cull)
+        c2ws = np.stack([_placed(c.detach().cpu().numpy() if torch.is_tensor(c) else c, scale, transform)
+                         for _, _, c in frames])
+        H, W = frames[0][0].shape[-2:]
+        if cull.get("method") == "occlusion" and cull.get("depths") is None:
+            cull["depths"] = [L.f32(d) * float(scale) if float(scale) != 1.0 else L.f32(d) for d, _, _ in frames]
+        vertices, faces, colors, _ = C.cull_mesh(vertices, faces, c2ws, _intrinsics(intrinsics), H, W, colors=colors, **cull)
+    if clean is not None and faces.shape[0] > 0:
+        vertices, faces, colors = C.clean_mesh(vertices, faces, colors, **clean)
+    return vertices, colors, faces
+
+
 # ---- PLY -------------------------------------------------------------------------------------------------------------
 _VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
 _FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
@@ -134,10 +154,11 @@ def save_mesh(output, vertices, colors, faces, mesh_name_suffix="kf", scene="sce
 
 def generate_mesh_kf(output, intrinsics, scale=1.0, transform=None, rendered_path="rendered_every_keyframe",
                      mesh_name_suffix="kf", scene="scene", voxel_length=5.0 / 512.0, sdf_trunc=0.04, device="cuda",
-                     max_blocks=None):
+                     max_blocks=None, cull=None, clean=None):
     """Reads output/{rendered_path}/{depth,color}_%05d.npy and output/video.npz; every map is matched to the keyframe
     pose with its timestamp (the reference's warm-up offset loop walks to the same pairs; a map without a keyframe is an
     error); depth and pose translation are multiplied by `scale`, then `transform` is applied (see the module text).
+    cull / clean: dicts of cull_mesh / clean_mesh keywords (cull_and_clean; off by default: the raw extraction).
     Writes mesh/{scene}_{suffix}.ply and mesh/vertices_pos_{suffix}.npy; -> (vertices, colors, faces) on the device"""
     maps_dir = os.path.join(str(output), rendered_path)
     stamps = sorted(int(m.group(1)) for m in (re.fullmatch(r"depth_(\d{5,})\.npy", f) for f in os.listdir(maps_dir)) if m)
@@ -152,5 +173,6 @@ def generate_mesh_kf(output, intrinsics, scale=1.0, transform=None, rendered_pat
         frames.append((depth, color, video["poses"][by_stamp[ts]]))
     vertices, colors, faces, _ = fuse_frames(frames, intrinsics, device, scale=scale, transform=transform,
                                              voxel_length=voxel_length, sdf_trunc=sdf_trunc, max_blocks=max_blocks)
+    vertices, colors, faces = cull_and_clean(vertices, colors, faces, frames, intrinsics, scale, transform, cull, clean)
     save_mesh(output, vertices, colors, faces, mesh_name_suffix, scene)
     return vertices, colors, faces

@@ -989,14 +989,17 @@ class SequenceRunner:
                                          npc_col_feats=npc.get_col_feats(), cloud_pos=npc.cloud_pos(), **kwargs)
 
     # ---- generate_mesh.py:55-123 ----------------------------------------------------------------------------------------
-    def mesh(self, output=None, mesh_name_suffix="kf", scene="scene", **kwargs):
+    def mesh(self, output=None, mesh_name_suffix="kf", scene="scene", cull=None, clean=None, **kwargs):
         """the triangle mesh of the run (generate_mesh.fuse_frames): every mapped keyframe is re-rendered (eval_kf_imgs)
         and its masked depth and colour are fused from device memory into a TSDF volume with the keyframe's own pose;
-        kwargs: scale, transform, voxel_length, sdf_trunc, max_blocks.  -> (vertices f32 [V,3], colors f32 [V,3], faces
-        int32 [F,3]) on the device; with `output` also mesh/{scene}_{suffix}.ply and mesh/vertices_pos_{suffix}.npy, as
-        generate_mesh_kf writes from the files of evaluate(output) and save_video.  Not part of run()"""
+        kwargs: scale, transform, voxel_length, sdf_trunc, max_blocks.  cull: a dict of cull_mesh.cull_mesh keywords - the
+        mesh is cut to what the mapped keyframes saw from their placed poses, for method "occlusion" against the masked
+        re-rendered depths; clean: a dict of cull_mesh.clean_mesh keywords (both off by default).  -> (vertices f32 [V,3],
+        colors f32 [V,3], faces int32 [F,3]) on the device; with `output` also mesh/{scene}_{suffix}.ply and
+        mesh/vertices_pos_{suffix}.npy, as generate_mesh_kf writes from the files of evaluate(output) and save_video.  Not
+        part of run()"""
         from .eval_render import eval_kf_imgs
-        from .generate_mesh import fuse_frames, save_mesh
+        from .generate_mesh import cull_and_clean, fuse_frames, save_mesh
         res = eval_kf_imgs(self, keep_renders=True)
         frames = []
         for f in res["frames"]:
@@ -1005,7 +1008,10 @@ class SequenceRunner:
             color = torch.where(r["mask"][..., None], r["color"].float(), torch.zeros_like(r["color"], dtype=torch.float32))
             frames.append((depth, color, self.video.get_pose(f["video_idx"], "cpu")))
         ren = self.renderer
-        vertices, colors, faces, _ = fuse_frames(frames, (ren.fx, ren.fy, ren.cx, ren.cy), self.device, **kwargs)
+        intrinsics = (ren.fx, ren.fy, ren.cx, ren.cy)
+        vertices, colors, faces, _ = fuse_frames(frames, intrinsics, self.device, **kwargs)
+        vertices, colors, faces = cull_and_clean(vertices, colors, faces, frames, intrinsics, kwargs.get("scale", 1.0),
+                                                 kwargs.get("transform"), cull, clean)
         if output is not None:
             save_mesh(output, vertices, colors, faces, mesh_name_suffix, scene)
         return vertices, colors, faces
@@ -1013,7 +1019,8 @@ class SequenceRunner:
     # ---- eval_recon.py:229-248 ------------------------------------------------------------------------------------------
     def recon(self, gt_vertices, gt_faces, output=None, mesh_kwargs=None, **kwargs):
         """the reconstruction scores of the run (eval_recon.eval_recon): the mesh of mesh(output=output, **mesh_kwargs)
-        against the ground-truth mesh (device tensors); kwargs: eval_2d, eval_3d, align, kwargs_3d, kwargs_2d.  -> the
+        against the ground-truth mesh (device tensors); kwargs: eval_2d, eval_3d, align, kwargs_3d, kwargs_2d, cull (views in
+        the ground truth's frame that both meshes are cut to before scoring).  -> the
         dict of accuracy, completion, completion_ratio, precision, recall, f-score and depth l1; with `output` also
         metrics_recon.txt next to the mesh folder.  Not part of run()"""
         from .eval_recon import eval_recon

@@ -1127,6 +1127,58 @@ int glorie_depth_l1_accumulate(const float* gt_depth, const float* rec_depth, in
                                int* valid, int view, void* stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Mesh culling to the seen region and removal of small components                       */
+/* ------------------------------------------------------------------------------------ */
+
+/* The conventions of the mesh-evaluation section hold: vertices f32 [V,3], faces int32 [F,3] and every w2c f32 [4,4] on
+ * the device, pixel (u, v) samples image coordinates (u, v), and a face with an index outside [0, V) is never read
+ * through: it is never kept, joins nothing and is counted nowhere.
+ *
+ * The views that see a vertex.  w2cs f32 [M,4,4]; depth_table: NULL (frustum only) or a DEVICE array of M `const float*`,
+ * depth maps f32 [H,W] (a null entry: frustum only for that view).  For view m and vertex X, in fp64 formed from the fp32
+ * inputs, every operation rounded on its own in the order written (the arithmetic of the check_proj kernel above):
+ *   p = ((R0 X.x + R1 X.y) + R2 X.z) + t per row;   in front: z_near < p.z <= z_far;
+ *   u = fx p.x / p.z + cx, v = fy p.y / p.z + cy;   ui = floor(u + 0.5), vi = floor(v + 0.5);
+ *   inside: edge <= ui < W - edge and edge <= vi < H - edge;
+ *   with a map: d = depth_m[vi,ui]; the view sees X when d > 0 and p.z <= d + eps; where d <= 0 (or NaN) it sees X only
+ *   if depth_missing_sees.
+ * count int32 [V]: count[i] = the number of views that see vertex i, added to what is there when accumulate = 1, so that
+ * chunks of views compose.  One thread owns a vertex and walks the views, whose matrices are staged in LDS 128 at a time:
+ * one launch for any M, no atomics, no host synchronisation.  edge >= 0, z_far > z_near, M >= 0. */
+int glorie_mesh_visibility(const float* vertices, int V, const float* w2cs, int M, float fx, float fy, float cx, float cy,
+                           int H, int W, float z_near, float z_far, int edge, const void* depth_table, float eps,
+                           int depth_missing_sees, int accumulate, int* count, void* stream);
+/* keep_face u8 [F]: 1 when all three (rule 0) or any (rule 1) of the face's vertices have count >= min_views, else 0.
+ * One launch. */
+int glorie_mesh_select_faces(const int* faces, int F, int V, const int* count, int min_views, int rule, uint8_t* keep_face,
+                             void* stream);
+/* The mesh under a face mask keep_face u8 [F] (any non-zero byte keeps).  Kept faces stay in their order; the vertices a
+ * kept face refers to stay in their order, the others are dropped; indices are remapped; colors f32 [V,3] (may be NULL)
+ * travel with the vertices.  The _count call fills the workspace and returns counts_out[0..1] = V', F' (HOST;
+ * synchronises the stream: the one read-back); the _emit call then writes out_vertices f32 [V',3], out_colors f32 [V',3]
+ * and out_faces int32 [F',3], sized by the caller, from the same workspace, mask and mesh.  V' = F' = 0 is no error and
+ * launches nothing.  Ballot counts and the scans of the TSDF extraction: integers, no atomics.
+ * workspace: glorie_mesh_compact_workspace(V, F) bytes. */
+size_t glorie_mesh_compact_workspace(int V, int F);
+int glorie_mesh_compact_count(const int* faces, int F, int V, const uint8_t* keep_face, void* workspace, int* counts_out,
+                              void* stream);
+int glorie_mesh_compact_emit(const float* vertices, const float* colors, const int* faces, int F, int V,
+                             const uint8_t* keep_face, void* workspace, int V_out, int F_out, float* out_vertices,
+                             float* out_colors, int* out_faces, void* stream);
+/* Connected components over shared vertex indices.
+ * label int32 [V] = the smallest vertex index of the vertex's component (a vertex no valid face touches is its own
+ * component); faces_of int32 [V] = the number of valid faces of the component at its label vertex, 0 elsewhere.
+ * keep_face u8 [F] (may be NULL: not computed): 1 for a valid face whose component has at least min_faces faces; with
+ * keep_largest = 1 additionally only for the component with the most faces, ties to the lower label.
+ * A lock-free union-find on `label`: links only ever point to a smaller index, the larger root is hooked under the smaller
+ * with a compare-and-swap, a flatten pass follows; every device loop ends for any input.  Integer atomics only: the
+ * outputs are the same bits in every run.  At most six launches, no host synchronisation.
+ * workspace: glorie_mesh_components_workspace() bytes, 8-byte aligned, need not be initialised. */
+size_t glorie_mesh_components_workspace(void);
+int glorie_mesh_components(const int* faces, int F, int V, int min_faces, int keep_largest, void* workspace, int* label,
+                           int* faces_of, uint8_t* keep_face, void* stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Ray gather of a window of keyframes (the final refinement)                            */
 /* ------------------------------------------------------------------------------------ */
 
