@@ -11,16 +11,16 @@
 //
 // Top-M selection, 12 launches whatever the data (records into a hipGraph), no host synchronisation:
 //   topm_init_kernel         the bins cleared, the rank M-1 from the top
-//   topm_hist_kernel x4      radix select of the M-th largest key over order-preserving uint keys, 8 bits per pass:
-//                            LDS bins, then one global integer atomic per bin and workgroup
+//   radix_hist_kernel x4     radix select of the M-th largest key over order-preserving uint keys, 8 bits per pass:
+//                            LDS bins, then one global integer atomic per bin and workgroup (radix.hiph)
 //   topm_pick_kernel x4      one wave: the bin holding the M-th largest key, the narrowed prefix, the histogram cleared
 //   topm_count_kernel        per workgroup: keys above the threshold key, keys equal to it, keys >= 0 (wave ballots)
 //   topm_scan_kernel         one workgroup: exclusive scans of the three counts, the valid count of the selection
 //   topm_write_kernel        every key above the threshold and the lowest-index `M - above` keys equal to it, written in
 //                            ascending index order
-// The float keys and the count, scan and rank steps are those of compact.hiph.
+// The float keys and the count, scan and rank steps are those of compact.hiph, the select's passes those of radix.hiph.
 // Every decision is an integer count: repeated calls are bitwise equal.
-#include "compact.hiph"
+#include "radix.hiph"
 
 using namespace glorie;
 
@@ -112,47 +112,20 @@ color_grad_maps_kernel(const float* __restrict__ img, int H, int W, int chw, con
 
 // state: [0] prefix of the threshold key, [1] rank still to skip from the top inside the prefix, [2] need (ties taken),
 // [3] -
-__global__ void __launch_bounds__(kTopThreads)
-topm_hist_kernel(const float* __restrict__ keys, int n, int pass, const unsigned int* __restrict__ state,
-                 unsigned int* __restrict__ hist) {
-  __shared__ unsigned int h[256];
-  h[threadIdx.x] = 0u;
-  __syncthreads();
-  const unsigned int mask = pass == 3 ? 0u : (0xffffffffu << (8 * (pass + 1)));
-  const unsigned int prefix = state[0];
-  for (int i = blockIdx.x * kTopThreads + threadIdx.x; i < n; i += gridDim.x * kTopThreads) {
-    const unsigned int k = float_key(keys[i]);
-    if ((k & mask) == prefix) atomicAdd(&h[(k >> (8 * pass)) & 255u], 1u);
-  }
-  __syncthreads();
-  if (h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
-}
-
 __global__ void __launch_bounds__(256)
 topm_init_kernel(unsigned int* __restrict__ hist, unsigned int* __restrict__ state, int M) {
   hist[threadIdx.x] = 0u;
   if (threadIdx.x < 4) state[threadIdx.x] = threadIdx.x == 1 ? (unsigned int)(M - 1) : 0u;
 }
 
-// one wave: walk the bins from the top, find the one holding the rank-th largest key, narrow the prefix, clear the bins
+// one wave: find the bin holding the rank-th largest key counted from the top, narrow the prefix, clear the bins
 __global__ void __launch_bounds__(64)
 topm_pick_kernel(unsigned int* __restrict__ state, unsigned int* __restrict__ hist, int pass) {
   __shared__ unsigned int bins[256];
-  for (int b = threadIdx.x; b < 256; b += 64) {
-    bins[b] = hist[b];
-    hist[b] = 0u;
-  }
-  __syncthreads();
+  const BinPick p = bin_pick_global(hist, bins, state[1], true);
   if (threadIdx.x == 0) {
-    unsigned int r = state[1];
-    int b = 255;
-    for (; b > 0; --b) {
-      const unsigned int c = bins[b];
-      if (r < c) break;
-      r -= c;
-    }
-    state[1] = r;
-    state[0] |= ((unsigned int)b & 255u) << (8 * pass);
+    state[1] = p.rank;
+    state[0] |= p.digit << (8 * pass);
   }
 }
 
@@ -180,19 +153,16 @@ topm_count_kernel(const float* __restrict__ keys, int n, const unsigned int* __r
 __global__ void __launch_bounds__(kScanThreads)
 topm_scan_kernel(int* cnt_gt, int* cnt_eq, const int* __restrict__ cnt_nonneg, int n_blocks, int M,
                  unsigned int* __restrict__ state, int* __restrict__ valid) {
-  __shared__ int red[kScanThreads / 64];
   const int* const in[2] = {cnt_gt, cnt_eq};
   int* const out[2] = {cnt_gt, cnt_eq};
   int above_equal[2];
   block_exclusive_scan<2>(in, out, n_blocks, above_equal);
   int nn = 0;
   for (int b = threadIdx.x; b < n_blocks; b += kScanThreads) nn += cnt_nonneg[b];
-  nn = wave_sum(nn);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = nn;
-  __syncthreads();
+  nn = block_sum<kScanThreads / 64>(nn);
   if (threadIdx.x == 0) {
     state[2] = (unsigned int)(M - above_equal[0]);
-    valid[0] = min(M, slot_sum(red, kScanThreads / 64));
+    valid[0] = min(M, nn);
   }
 }
 
@@ -225,6 +195,17 @@ RadiusMap make_map(double rmax, double rmin, double thr) {
   return m;
 }
 
+// workspace: hist uint [256] | state uint [4] | cnt_gt, cnt_eq, cnt_nonneg int [B] each
+struct TopmWs {
+  Carver c;
+  int n;
+  unsigned int* hist = c.take<unsigned int>(256);
+  unsigned int* state = c.take<unsigned int>(4);
+  int* cnt_gt = c.take<int>(top_blocks(n));
+  int* cnt_eq = c.take<int>(top_blocks(n));
+  int* cnt_nn = c.take<int>(top_blocks(n));
+};
+
 }  // namespace
 
 extern "C" int glorie_color_grad_maps(const float* image, int H, int W, int channels_first,
@@ -244,12 +225,7 @@ extern "C" int glorie_color_grad_maps(const float* image, int H, int W, int chan
   return check_launch();
 }
 
-// workspace: hist uint [256] | state uint [4] | cnt_gt, cnt_eq, cnt_nonneg int [B] each
-extern "C" size_t glorie_topm_workspace(int n) {
-  if (n < 0) return 0;
-  const size_t B = (size_t)top_blocks(n);
-  return 256 * sizeof(unsigned int) + 4 * sizeof(unsigned int) + 3 * align8(B * sizeof(int));
-}
+extern "C" size_t glorie_topm_workspace(int n) { return n < 0 ? 0 : carved_bytes<TopmWs>(n); }
 
 extern "C" int glorie_topm(const float* keys, int n, int M, void* workspace, int64_t* indices, int* valid_count,
                            void* stream) {
@@ -259,28 +235,25 @@ extern "C" int glorie_topm(const float* keys, int n, int M, void* workspace, int
   if (M == 0) return check_hip(hipMemsetAsync(valid_count, 0, sizeof(int), st));
   if (!keys || !workspace || !indices) return GLORIE_EINVAL;
   const int B = top_blocks(n);
-  char* ws = reinterpret_cast<char*>(workspace);
-  unsigned int* hist = reinterpret_cast<unsigned int*>(ws);
-  unsigned int* state = hist + 256;
-  int* cnt_gt = reinterpret_cast<int*>(state + 4);
-  int* cnt_eq = reinterpret_cast<int*>(reinterpret_cast<char*>(cnt_gt) + align8((size_t)B * sizeof(int)));
-  int* cnt_nn = reinterpret_cast<int*>(reinterpret_cast<char*>(cnt_eq) + align8((size_t)B * sizeof(int)));
+  const TopmWs w{Carver(workspace), n};
   // state = {prefix 0, rank M-1 from the top, -, -}, bins cleared
-  hipLaunchKernelGGL(topm_init_kernel, dim3(1), dim3(256), 0, st, hist, state, M);
+  hipLaunchKernelGGL(topm_init_kernel, dim3(1), dim3(256), 0, st, w.hist, w.state, M);
   GLORIE_TRY(check_launch());
-  const int hb = (n + kTopThreads * kHistItems - 1) / (kTopThreads * kHistItems);
+  const int hb = (n + kHistThreads * kHistItems - 1) / (kHistThreads * kHistItems);
   for (int pass = 3; pass >= 0; --pass) {
-    hipLaunchKernelGGL(topm_hist_kernel, dim3(hb), dim3(kTopThreads), 0, st, keys, n, pass, state, hist);
+    hipLaunchKernelGGL(radix_hist_kernel<FloatKeys>, dim3(hb), dim3(kHistThreads), 0, st, FloatKeys{keys}, n, pass,
+                       w.state, 0, w.hist);
     GLORIE_TRY(check_launch());
-    hipLaunchKernelGGL(topm_pick_kernel, dim3(1), dim3(64), 0, st, state, hist, pass);
+    hipLaunchKernelGGL(topm_pick_kernel, dim3(1), dim3(64), 0, st, w.state, w.hist, pass);
     GLORIE_TRY(check_launch());
   }
-  hipLaunchKernelGGL(topm_count_kernel, dim3(B), dim3(kTopThreads), 0, st, keys, n, state, cnt_gt, cnt_eq, cnt_nn);
+  hipLaunchKernelGGL(topm_count_kernel, dim3(B), dim3(kTopThreads), 0, st, keys, n, w.state, w.cnt_gt, w.cnt_eq,
+                     w.cnt_nn);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(topm_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, cnt_gt, cnt_eq, cnt_nn, B, M, state,
+  hipLaunchKernelGGL(topm_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, w.cnt_gt, w.cnt_eq, w.cnt_nn, B, M, w.state,
                      valid_count);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(topm_write_kernel, dim3(B), dim3(kTopThreads), 0, st, keys, n, state, cnt_gt, cnt_eq, M,
+  hipLaunchKernelGGL(topm_write_kernel, dim3(B), dim3(kTopThreads), 0, st, keys, n, w.state, w.cnt_gt, w.cnt_eq, M,
                      indices);
   return check_launch();
 }

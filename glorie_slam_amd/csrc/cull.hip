@@ -111,33 +111,16 @@ mesh_select_faces_kernel(const int* __restrict__ faces, int F, int V, const int*
 
 // ---- compaction -------------------------------------------------------------------------------------------------------------
 struct CompactWs {
-  int* used;          // [V] 1 where a kept face refers to the vertex
-  int* new_index;     // [V]
-  int* wgc_v;         // [Bv] marks per workgroup, then their exclusive scan in wgo_v
-  int* wgo_v;
-  int* wgc_f;         // [Bf]
-  int* wgo_f;
-  int* totals;        // [2] V', F'
+  Carver c;
+  int V, F;
+  int* used = c.take<int>(V);                  // [V] 1 where a kept face refers to the vertex
+  int* new_index = c.take<int>(V);             // [V]
+  int* wgc_v = c.take<int>(blocks_of(V));      // [Bv] marks per workgroup, then their exclusive scan in wgo_v
+  int* wgo_v = c.take<int>(blocks_of(V));
+  int* wgc_f = c.take<int>(blocks_of(F));      // [Bf]
+  int* wgo_f = c.take<int>(blocks_of(F));
+  int* totals = c.take<int>(2);                // [2] V', F'
 };
-
-CompactWs carve_compact(void* workspace, int V, int F) {
-  CompactWs w;
-  char* p = reinterpret_cast<char*>(workspace);
-  auto take = [&](size_t n) {
-    int* q = reinterpret_cast<int*>(p);
-    p += align8(n * sizeof(int));
-    return q;
-  };
-  const int bv = blocks_of(V), bf = blocks_of(F);
-  w.used = take(V);
-  w.new_index = take(V);
-  w.wgc_v = take(bv);
-  w.wgo_v = take(bv);
-  w.wgc_f = take(bf);
-  w.wgo_f = take(bf);
-  w.totals = take(2);
-  return w;
-}
 
 __device__ __forceinline__ bool face_kept(const int* __restrict__ faces, int F, int V,
                                           const unsigned char* __restrict__ keep_face, int f, FaceIdx* t) {
@@ -404,20 +387,17 @@ extern "C" int glorie_mesh_select_faces(const int* faces, int F, int V, const in
   return check_launch();
 }
 
-// workspace: used int [V] | new_index int [V] | marks per workgroup and their offsets int [Bv] x 2 | kept faces per
-// workgroup and their offsets int [Bf] x 2 | totals int [2], every piece 8-byte aligned
+// workspace (CompactWs): used int [V] | new_index int [V] | marks per workgroup and their offsets int [Bv] x 2 | kept faces
+// per workgroup and their offsets int [Bf] x 2 | totals int [2], every piece 8-byte aligned
 extern "C" size_t glorie_mesh_compact_workspace(int V, int F) {
-  if (V <= 0 || F <= 0) return 0;
-  const size_t bv = blocks_of(V), bf = blocks_of(F);
-  return 2 * align8((size_t)V * sizeof(int)) + 2 * align8(bv * sizeof(int)) + 2 * align8(bf * sizeof(int)) +
-         align8(2 * sizeof(int));
+  return (V <= 0 || F <= 0) ? 0 : carved_bytes<CompactWs>(V, F);
 }
 
 extern "C" int glorie_mesh_compact_count(const int* faces, int F, int V, const uint8_t* keep_face, void* workspace,
                                          int* counts_out, void* stream) {
   if (V <= 0 || F <= 0 || !faces || !keep_face || !workspace || !counts_out) return GLORIE_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const CompactWs w = carve_compact(workspace, V, F);
+  const CompactWs w{Carver(workspace), V, F};
   const int bv = blocks_of(V), bf = blocks_of(F);
   counts_out[0] = counts_out[1] = 0;
   GLORIE_TRY(check_hip(hipMemsetAsync(w.used, 0, (size_t)V * sizeof(int), st)));
@@ -440,7 +420,7 @@ extern "C" int glorie_mesh_compact_emit(const float* vertices, const float* colo
   if (V_out == 0 && F_out == 0) return GLORIE_OK;
   if ((V_out > 0 && !out_vertices) || (F_out > 0 && !out_faces) || (colors && V_out > 0 && !out_colors)) return GLORIE_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const CompactWs w = carve_compact(workspace, V, F);
+  const CompactWs w{Carver(workspace), V, F};
   hipLaunchKernelGGL(compact_emit_vertices_kernel, dim3(blocks_of(V)), dim3(kThreads), 0, st, vertices, colors, V, w.used,
                      w.wgo_v, V_out, w.new_index, out_vertices, out_colors);
   GLORIE_TRY(check_launch());

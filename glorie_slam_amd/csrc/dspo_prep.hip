@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
-#include "common.hiph"
+#include "radix.hiph"
 
 extern "C" int glorie_depth_filter(const float* poses, const float* disps, const float* intrinsics,
                                    const int64_t* ix, const float* thresh, float* count, int B, int num,
@@ -21,23 +21,16 @@ extern "C" int glorie_depth_filter(const float* poses, const float* disps, const
 
 namespace glorie {
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  // 1024 threads = 16 waves; fixed order -> deterministic
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];
-  return s;
-}
+// threads of the per-frame kernels below: their launch bounds, their launches and the waves block_sum_all joins
+constexpr int kPrepThreads = 1024;
 
-__global__ __launch_bounds__(1024) void prep_stats_kernel(const float* __restrict__ disps, int HW,
+// the sum over a workgroup of kPrepThreads (16 waves) on every thread; fixed order -> deterministic
+__device__ __forceinline__ double block_sum_all(double v) { return block_reduce_all<kPrepThreads / 64, SumOp>(v); }
+
+__global__ __launch_bounds__(kPrepThreads) void prep_stats_kernel(const float* __restrict__ disps, int HW,
                                                           float mv_thresh, float* __restrict__ thresh,
                                                           float* __restrict__ avg_disp,
                                                           int64_t* __restrict__ ix, int* __restrict__ any_on) {
-  __shared__ double red[16];
   const int f = blockIdx.x;
   if (f == 0 && threadIdx.x == 0) *any_on = 0;      // prep_edges_kernel ORs into it three launches later (no memset node)
   const float* d = disps + (size_t)f * HW;
@@ -47,8 +40,8 @@ __global__ __launch_bounds__(1024) void prep_stats_kernel(const float* __restric
     sd += (double)v;
     sz += (double)(1.0f / v);
   }
-  const double td = block_sum(sd, red);
-  const double tz = block_sum(sz, red);
+  const double td = block_sum_all(sd);
+  const double tz = block_sum_all(sz);
   if (threadIdx.x == 0) {
     thresh[f] = mv_thresh * (float)(tz / (double)HW);
     avg_disp[f] = (float)(td / (double)HW);
@@ -57,15 +50,14 @@ __global__ __launch_bounds__(1024) void prep_stats_kernel(const float* __restric
 }
 
 // dynamic LDS: HW keys (uint32)
-__global__ __launch_bounds__(1024) void prep_align_kernel(
+__global__ __launch_bounds__(kPrepThreads) void prep_align_kernel(
     const float* __restrict__ disps, const float* __restrict__ mono, const float* __restrict__ count,
     const float* __restrict__ avg_disp, int HW, float visible, float mono_thres,
     uint8_t* __restrict__ valid_mask, float* __restrict__ scales, float* __restrict__ shifts,
     uint8_t* __restrict__ bad) {
   extern __shared__ uint32_t keys[];
-  __shared__ double red[16];
   __shared__ unsigned hist[256];
-  __shared__ unsigned sel_prefix, sel_k, wsum[4];
+  __shared__ unsigned sel_prefix, sel_k;
   const int f = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const float* d = disps + (size_t)f * HW;
   const float* m = mono + (size_t)f * HW;
@@ -79,7 +71,7 @@ __global__ __launch_bounds__(1024) void prep_align_kernel(
     keys[k] = (ok && !isnan(z)) ? __float_as_uint(z) : 0xffffffffu;
     nv += (ok && !isnan(z)) ? 1.0 : 0.0;
   }
-  const int nvalid = (int)block_sum(nv, red);
+  const int nvalid = (int)block_sum_all(nv);
   float med = nanf("");
   if (nvalid > 0) {
     if (tid == 0) { sel_prefix = 0u; sel_k = (unsigned)((nvalid - 1) / 2); }   // lower median
@@ -93,25 +85,11 @@ __global__ __launch_bounds__(1024) void prep_align_kernel(
         if (key != 0xffffffffu && (key & mask) == prefix) atomicAdd(&hist[(key >> (8 * pass)) & 255u], 1u);
       }
       __syncthreads();
-      {
-        // which bin holds the k-th key: inclusive scan of the 256 bins over the first 4 waves
-        const unsigned kk = sel_k;
-        const unsigned hv = tid < 256 ? hist[tid] : 0u;
-        unsigned incl = hv;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const unsigned v = __shfl_up(incl, off, 64);
-          if ((tid & 63) >= off) incl += v;
-        }
-        if (tid < 256 && (tid & 63) == 63) wsum[tid >> 6] = incl;
-        __syncthreads();
-        if (tid < 256) {
-          for (int q = 0; q < (tid >> 6); ++q) incl += wsum[q];
-          const unsigned excl = incl - hv;
-          if (kk >= excl && kk < incl) {          // exactly one bin (the k-th key exists: nvalid > k)
-            sel_k = kk - excl;
-            sel_prefix = prefix | ((unsigned)tid << (8 * pass));
-          }
+      if (tid < 64) {                             // wave 0: which bin holds the k-th key
+        const BinPick p = bin_pick(hist, sel_k);
+        if (tid == 0 && p.digit != 256u) {        // always one (the k-th key exists: nvalid > k)
+          sel_k = p.rank;
+          sel_prefix = prefix | (p.digit << (8 * pass));
         }
       }
       mask |= 0xffu << (8 * pass);
@@ -135,8 +113,8 @@ __global__ __launch_bounds__(1024) void prep_align_kernel(
       b1 += (double)t;
     }
   }
-  const float A00 = (float)block_sum(a00, red), A01 = (float)block_sum(a01, red);
-  const float A11 = (float)block_sum(a11, red), B0 = (float)block_sum(b0, red), B1 = (float)block_sum(b1, red);
+  const float A00 = (float)block_sum_all(a00), A01 = (float)block_sum_all(a01);
+  const float A11 = (float)block_sum_all(a11), B0 = (float)block_sum_all(b0), B1 = (float)block_sum_all(b1);
   const float det = A00 * A11 - A01 * A01;
   const float scale = (A11 * B0 - A01 * B1) / det;
   const float shift = (-A01 * B0 + A00 * B1) / det;
@@ -145,7 +123,7 @@ __global__ __launch_bounds__(1024) void prep_align_kernel(
     const unsigned key = keys[k];
     if (key != 0xffffffffu && __uint_as_float(key) < lim) es += (double)fabsf(scale * m[k] + shift - d[k]);
   }
-  const float err = (float)block_sum(es, red) / A11;
+  const float err = (float)block_sum_all(es) / A11;
   if (tid == 0) {
     scales[f] = scale;
     shifts[f] = shift;
@@ -201,16 +179,15 @@ __global__ void publish_flag_kernel(const int* __restrict__ flag, int* __restric
 // Two-view validity mask for an arbitrary frame list and map size (scope row N4:
 // DepthVideo.update_valid_depth_mask(up=True) at full resolution, depth_video.py:326-361): the
 // nanmedian of 307,200 depths per frame does not fit LDS, so the radix select runs over global keys:
-// per pass one histogram kernel (LDS bins -> global atomics) and one 1-thread-per-frame bin pick.
+// per pass the histogram kernel of radix.hiph (LDS bins -> global atomics) and a one-wave-per-frame bin pick.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void vmask_stats_kernel(const float* __restrict__ disps,
+__global__ __launch_bounds__(kPrepThreads) void vmask_stats_kernel(const float* __restrict__ disps,
                                                            const int64_t* __restrict__ ix, int HW,
                                                            float mv_thresh, float* __restrict__ thresh) {
-  __shared__ double red[16];
   const float* d = disps + (size_t)ix[blockIdx.x] * HW;
   double sz = 0.0;
   for (int k = threadIdx.x; k < HW; k += blockDim.x) sz += (double)(1.0f / d[k]);
-  const double tz = block_sum(sz, red);
+  const double tz = block_sum_all(sz);
   if (threadIdx.x == 0) thresh[blockIdx.x] = mv_thresh * (float)(tz / (double)HW);
 }
 
@@ -232,38 +209,17 @@ __global__ __launch_bounds__(256) void vmask_keys_kernel(const float* __restrict
   if ((threadIdx.x & 63) == 0 && b) atomicAdd(&sel[f * 4 + 0], (unsigned)__popcll(b));
 }
 
-__global__ __launch_bounds__(256) void vmask_hist_kernel(const uint32_t* __restrict__ keys, int HW, int pass,
-                                                         const unsigned* __restrict__ sel,
-                                                         unsigned* __restrict__ hist /*[num][256]*/) {
-  __shared__ unsigned h[256];
-  const int f = blockIdx.y;
-  h[threadIdx.x] = 0u;
-  __syncthreads();
-  const unsigned mask = pass == 3 ? 0u : (0xffffffffu << (8 * (pass + 1)));
-  const unsigned prefix = sel[f * 4 + 2];
-  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
-    const unsigned key = keys[(size_t)f * HW + p];
-    if (key != 0xffffffffu && (key & mask) == prefix) atomicAdd(&h[(key >> (8 * pass)) & 255u], 1u);
+// one wave per frame: pick the bin holding the k-th key, narrow the prefix, clear the histogram
+__global__ __launch_bounds__(64) void vmask_pick_kernel(unsigned* __restrict__ sel, unsigned* __restrict__ hist,
+                                                        int pass) {
+  __shared__ unsigned bins[256];
+  unsigned* s = sel + 4 * blockIdx.x;
+  const unsigned k = pass == 3 ? (s[0] ? (s[0] - 1) / 2 : 0) : s[1];               // lower median
+  const BinPick p = bin_pick_global(hist + 256 * blockIdx.x, bins, k, false);
+  if (threadIdx.x == 0) {
+    s[1] = p.rank;
+    s[2] |= p.digit << (8 * pass);
   }
-  __syncthreads();
-  if (h[threadIdx.x]) atomicAdd(&hist[f * 256 + threadIdx.x], h[threadIdx.x]);
-}
-
-// one thread per frame: pick the bin holding the k-th key, narrow the prefix, clear the histogram
-__global__ void vmask_pick_kernel(unsigned* __restrict__ sel, unsigned* __restrict__ hist, int num, int pass) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= num) return;
-  if (pass == 3) sel[f * 4 + 1] = sel[f * 4 + 0] ? (sel[f * 4 + 0] - 1) / 2 : 0;   // lower median
-  unsigned kk = sel[f * 4 + 1], b = 0;
-  for (; b < 256; ++b) {
-    const unsigned c = hist[f * 256 + b];
-    hist[f * 256 + b] = 0u;
-    if (kk < c) break;
-    kk -= c;
-  }
-  for (unsigned r = b + 1; r < 256; ++r) hist[f * 256 + r] = 0u;
-  sel[f * 4 + 1] = kk;
-  sel[f * 4 + 2] |= (b & 255u) << (8 * pass);
 }
 
 __global__ __launch_bounds__(256) void vmask_write_kernel(const uint32_t* __restrict__ keys, int HW,
@@ -308,10 +264,10 @@ extern "C" int glorie_dspo_prepare(const float* poses, const float* disps, const
   float* avg = thresh + n;
   int64_t* ix = reinterpret_cast<int64_t*>(sp + ((((size_t)n * HW + 2 * n) * 4 + 7) / 8) * 8);
   uint8_t* bad = reinterpret_cast<uint8_t*>(ix + n);
-  hipLaunchKernelGGL(prep_stats_kernel, dim3(n), dim3(1024), 0, st, disps, HW, mv_thresh, thresh, avg, ix, any_on);
+  hipLaunchKernelGGL(prep_stats_kernel, dim3(n), dim3(kPrepThreads), 0, st, disps, HW, mv_thresh, thresh, avg, ix, any_on);
   GLORIE_TRY(glorie_depth_filter(poses, disps, intrinsics, ix, thresh, count, B, n, h, w, stream));
   GLORIE_TRY(lds_opt_in<prep_align_kernel>(150 * 1024));
-  hipLaunchKernelGGL(prep_align_kernel, dim3(n), dim3(1024), (size_t)HW * 4, st, disps, mono_disps, count, avg,
+  hipLaunchKernelGGL(prep_align_kernel, dim3(n), dim3(kPrepThreads), (size_t)HW * 4, st, disps, mono_disps, count, avg,
                      HW, (float)visible_num, mono_thres, valid_mask, scales, shifts, bad);
   if (N > 0)
     hipLaunchKernelGGL(prep_edges_kernel, dim3((N + 255) / 256), dim3(256), 0, st, bad, ii, jj, N, n, edge_on,
@@ -341,16 +297,16 @@ extern "C" int glorie_valid_depth_mask(const float* poses, const float* disps, c
   unsigned* sel = reinterpret_cast<unsigned*>(thresh + num);
   unsigned* hist = sel + (size_t)num * 4;
   GLORIE_TRY(check_hip(hipMemsetAsync(sel, 0, sizeof(unsigned) * ((size_t)num * 4 + (size_t)num * 256), st)));
-  hipLaunchKernelGGL(vmask_stats_kernel, dim3(num), dim3(1024), 0, st, disps, ix, HW, mv_thresh, thresh);
+  hipLaunchKernelGGL(vmask_stats_kernel, dim3(num), dim3(kPrepThreads), 0, st, disps, ix, HW, mv_thresh, thresh);
   GLORIE_TRY(glorie_depth_filter(poses, disps, intrinsics, ix, thresh, count, B, num, h, w, stream));
   const dim3 pix((HW + 255) / 256, num);
   hipLaunchKernelGGL(vmask_keys_kernel, pix, dim3(256), 0, st, disps, ix, HW, (float)visible_num,
                      reinterpret_cast<uint32_t*>(count), sel);
   const int hb = (HW + 256 * 8 - 1) / (256 * 8);
   for (int pass = 3; pass >= 0; --pass) {
-    hipLaunchKernelGGL(vmask_hist_kernel, dim3(hb, num), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(count),
-                       HW, pass, sel, hist);
-    hipLaunchKernelGGL(vmask_pick_kernel, dim3((num + 63) / 64), dim3(64), 0, st, sel, hist, num, pass);
+    hipLaunchKernelGGL(radix_hist_kernel<RawKeys>, dim3(hb, num), dim3(kHistThreads), 0, st,
+                       RawKeys{reinterpret_cast<const uint32_t*>(count)}, HW, pass, sel, 2, hist);
+    hipLaunchKernelGGL(vmask_pick_kernel, dim3(num), dim3(64), 0, st, sel, hist, pass);
   }
   hipLaunchKernelGGL(vmask_write_kernel, pix, dim3(256), 0, st, reinterpret_cast<const uint32_t*>(count), HW, sel,
                      mask);

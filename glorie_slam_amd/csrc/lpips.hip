@@ -20,7 +20,7 @@
 // Score (lpips_score_kernel, one launch for the five taps; lpips_finish_kernel): a wave per pixel forms both channel
 //   norms, the normalised difference and the lin-weighted sum in fp64; per-workgroup partials are added in a fixed order
 //   (ordered_sum).  No atomics, no host synchronisation, no allocation: everything records into a hipGraph.
-#include "common.hiph"
+#include "compact.hiph"
 
 using namespace glorie;
 
@@ -252,7 +252,6 @@ struct ScoreArgs {
 
 // partial[tap][block] = sum over the block's pixels of sum_c lin[c] (f_x / |f_x| - f_y / |f_y|)^2; a wave per pixel
 __global__ void __launch_bounds__(kThreads) lpips_score_kernel(ScoreArgs a, double* __restrict__ partial) {
-  __shared__ double red[kThreads / 64];
   const int tap = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int npx = a.npx[tap], C = a.c[tap];
   const float* __restrict__ fx = a.f[tap];
@@ -281,13 +280,10 @@ __global__ void __launch_bounds__(kThreads) lpips_score_kernel(ScoreArgs a, doub
     }
     sum += wave_sum(s);
   }
-  if (lane == 0) red[wave] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < kThreads / 64; ++i) t += red[i];
-    partial[(size_t)tap * gridDim.x + blockIdx.x] = t;
-  }
+  // every lane of a wave holds the wave's sum already: lane 0's goes into the workgroup sum.  The butterfly then only adds
+  // zeros (same bits; 8 more VGPRs, occupancy unchanged): the price of one reduction helper instead of a store-only variant
+  const double t = block_sum<kThreads / 64>(lane == 0 ? sum : 0.0);
+  if (threadIdx.x == 0) partial[(size_t)tap * gridDim.x + blockIdx.x] = t;
 }
 
 // out[1 + l] = mean over the pixels of tap l; out[0] = their sum
@@ -333,6 +329,21 @@ bool make_net(int H, int W, Net* net) {
 inline size_t partial_doubles(const Net& n) { return ((size_t)kLayers * n.score_blocks + 1) & ~(size_t)1; }
 inline size_t map_floats(const Net& n, int l) { return 2 * (size_t)n.h[l] * n.w[l] * kNet[l].co; }
 inline size_t pooled_floats(const Net& n, int i) { return 2 * (size_t)n.ph[i] * n.pw[i] * kNet[i].co; }
+inline size_t own_floats(const Net& n) {
+  size_t f = 0;
+  for (int l = 0; l < kLayers; ++l) f += map_floats(n, l);
+  return f;
+}
+
+// workspace: partials double [5][score_blocks] | the five feature maps | the two pooled maps.  Every piece is a multiple of
+// 16 bytes (an even count of doubles, channel counts that are multiples of 4), which the float4 accesses of the maps need
+struct LpipsWs {
+  Carver c;
+  Net net;
+  double* partial = c.take<double>(partial_doubles(net));
+  float* own = c.take<float>(own_floats(net));
+  float* pooled[2] = {c.take<float>(pooled_floats(net, 0)), c.take<float>(pooled_floats(net, 1))};
+};
 
 template <int MODE, int BM>
 int launch_conv(const ConvArgs& a, hipStream_t st) {
@@ -361,13 +372,9 @@ extern "C" int glorie_lpips_shapes(int H, int W, int* hw) {
   return GLORIE_OK;
 }
 
-// workspace: partials double [5][score_blocks] | the five feature maps | the two pooled maps
 extern "C" size_t glorie_lpips_workspace(int H, int W) {
   Net net;
-  if (!make_net(H, W, &net)) return 0;
-  size_t floats = pooled_floats(net, 0) + pooled_floats(net, 1);
-  for (int l = 0; l < kLayers; ++l) floats += map_floats(net, l);
-  return partial_doubles(net) * sizeof(double) + floats * sizeof(float);
+  return make_net(H, W, &net) ? carved_bytes<LpipsWs>(net) : 0;
 }
 
 extern "C" int glorie_lpips(const float* x, const float* y, int H, int W, int channels_first, const float* weights,
@@ -379,13 +386,11 @@ extern "C" int glorie_lpips(const float* x, const float* y, int H, int W, int ch
   if (!make_net(H, W, &net)) return GLORIE_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const bool fold = (flags & GLORIE_LPIPS_FOLD_POOLS) != 0;
-  double* partial = reinterpret_cast<double*>(workspace);
-  float* fl = reinterpret_cast<float*>(partial + partial_doubles(net));
-  float* own = fl;
-  for (int l = 0; l < kLayers; ++l) fl += map_floats(net, l);
-  float* pooled[2] = {fl, fl + pooled_floats(net, 0)};
+  const LpipsWs ws{Carver(workspace), net};
+  double* partial = ws.partial;
+  float* const* pooled = ws.pooled;
   float* maps[kLayers];
-  float* base = features ? features : own;
+  float* base = features ? features : ws.own;
   for (int l = 0; l < kLayers; ++l) {
     maps[l] = base;
     base += map_floats(net, l);

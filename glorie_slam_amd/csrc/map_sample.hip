@@ -18,9 +18,11 @@
 //                         float bits (positive floats order as unsigned integers; 8 bits per pass, 4 passes), their
 //                         maximum, the threshold, and keep = depth > 0 && depth <= threshold as 1 / 0 weights.  One
 //                         workgroup; a wave counts a digit with eight ballots (the lanes that share a digit elect one
-//                         of them to add their number to the wave's own LDS histogram), so there is no atomic.
+//                         of them to add their number to the wave's own LDS histogram), so there is no atomic; the bin
+//                         that holds the rank is picked by radix.hiph's bin_pick.
 //
 // No host synchronisation, no atomics, no output sized by the data; every launch is on the caller's stream.
+#include "radix.hiph"
 #include "window_rays.hiph"
 
 using namespace glorie;
@@ -140,9 +142,7 @@ __global__ void __launch_bounds__(kGateWaves * 64)
 depth_gate_kernel(const float* __restrict__ depth, int N, float* __restrict__ keep, float* __restrict__ stats) {
   __shared__ unsigned int hist[kGateWaves][256];
   __shared__ unsigned int total[256];
-  __shared__ unsigned int wave_max_bits[kGateWaves];
-  __shared__ unsigned int wave_kept[kGateWaves];
-  __shared__ unsigned int pick[2];                                    // the selected digit, the count below it
+  __shared__ unsigned int pick[2];                                    // the selected digit, the rank inside it
   constexpr int T = kGateWaves * 64;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
@@ -170,10 +170,6 @@ depth_gate_kernel(const float* __restrict__ depth, int N, float* __restrict__ ke
       }
       if (in && lane == __ffsll((long long)peers) - 1) hist[wave][digit] += (unsigned int)__popcll(peers);
     }
-    if (pass == 0) {
-      max_bits = wave_max(max_bits);
-      if (lane == 0) wave_max_bits[wave] = max_bits;
-    }
     __syncthreads();
     if (tid < 256) {
       unsigned int s = 0u;
@@ -182,36 +178,13 @@ depth_gate_kernel(const float* __restrict__ depth, int N, float* __restrict__ ke
       total[tid] = s;
     }
     __syncthreads();
-    if (wave == 0) {                                                  // lane l scans digits 4l .. 4l+3
-      unsigned int a[4], s = 0u;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        a[q] = total[4 * lane + q];
-        s += a[q];
-      }
-      unsigned int incl = s;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned int up = (unsigned int)__shfl_up((int)incl, off, 64);
-        if (lane >= off) incl += up;
-      }
-      const unsigned int n_in = (unsigned int)__shfl((int)incl, 63, 64);   // pass 0: the number of positive depths
-      unsigned int want = pass == 0 ? (n_in ? (n_in - 1u) / 2u : 0u) : kth;
-      unsigned int cum = incl - s;
-      if (n_in == 0u) {
-        if (lane == 0) {
-          pick[0] = 256u;                                             // no positive depth at all
-          pick[1] = 0u;
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (want >= cum && want < cum + a[q]) {                     // exactly one lane and q
-            pick[0] = 4u * lane + q;
-            pick[1] = want - cum;
-          }
-          cum += a[q];
-        }
+    if (wave == 0) {
+      // pass 0: the bins hold every positive depth, the rank is their lower median's; no positive depth at all: digit 256
+      const BinPick p =
+          bin_pick(total, [=](unsigned int n_in) { return pass == 0 ? (n_in ? (n_in - 1u) / 2u : 0u) : kth; });
+      if (lane == 0) {
+        pick[0] = p.digit;
+        pick[1] = p.rank;
       }
     }
     __syncthreads();
@@ -220,9 +193,7 @@ depth_gate_kernel(const float* __restrict__ depth, int N, float* __restrict__ ke
     kth = pick[1];
   }
   const bool none = pick[0] == 256u;
-  unsigned int mx = 0u;
-#pragma unroll
-  for (int q = 0; q < kGateWaves; ++q) mx = max(mx, wave_max_bits[q]);
+  const unsigned int mx = block_reduce_all<kGateWaves, MaxOp>(max_bits);
 
   float median = 0.0f, dmax = 0.0f, thr = 0.0f;
   if (!none) {
@@ -230,19 +201,15 @@ depth_gate_kernel(const float* __restrict__ depth, int N, float* __restrict__ ke
     dmax = __uint_as_float(mx);
     thr = fminf(10.0f * median, 1.2f * dmax);                         // two single products: nothing to contract
   }
-  unsigned int kept = 0u;
+  int kept = 0;
   for (int idx = tid; idx < N; idx += T) {
     const float d = depth[idx];
     const bool k = !none && d > 0.0f && d <= thr;
     keep[idx] = k ? 1.0f : 0.0f;
-    kept += k ? 1u : 0u;
+    kept += k ? 1 : 0;
   }
-  kept = (unsigned int)wave_sum((int)kept);
-  if (lane == 0) wave_kept[wave] = kept;
-  __syncthreads();
+  const int all = block_sum<kGateWaves>(kept);
   if (tid == 0) {
-    unsigned int all = 0u;
-    for (int q = 0; q < kGateWaves; ++q) all += wave_kept[q];
     stats[0] = median;
     stats[1] = dmax;
     stats[2] = thr;

@@ -13,7 +13,7 @@
 //   the mask, the mask count, |depth - gt_depth| over the mask; fp32 differences accumulated in fp64.
 // No floating-point atomics anywhere: every sum is a per-workgroup partial added in a fixed order (ordered_sum), so
 // repeated calls are bitwise equal.  No host synchronisation, no allocation: everything records into a hipGraph.
-#include "common.hiph"
+#include "compact.hiph"
 
 using namespace glorie;
 
@@ -29,7 +29,6 @@ constexpr int kHSeg = 4;                      // outputs per thread along a row,
 constexpr int kVSeg = 2;                      // outputs per thread along a column, vertical pass
 constexpr int kMaxLevels = 5;
 constexpr double kC1 = 1e-4, kC2 = 9e-4;      // (0.01 * data_range)^2, (0.03 * data_range)^2 with data_range 1
-constexpr int kReduceBlocks = 1024;           // cap of the frame-sum grid
 
 static_assert(kTW * (kTH / kVSeg) == kThreads, "vertical pass: one thread per column and row pair");
 static_assert(kTW % kHSeg == 0 && kTH % kVSeg == 0, "segments tile the output");
@@ -69,7 +68,6 @@ ms_ssim_level_kernel(const float* __restrict__ x, const float* __restrict__ y, i
                      double* __restrict__ partial, float* __restrict__ next_x, float* __restrict__ next_y) {
   __shared__ float sx[kInH][kInW + 1], sy[kInH][kInW + 1];
   __shared__ double hp[5][kInH][kTW + 1];
-  __shared__ double red[2][kWaves];
   const int tid = threadIdx.x;
   const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
   if (blockIdx.z >= 3) {
@@ -157,16 +155,9 @@ ms_ssim_level_kernel(const float* __restrict__ x, const float* __restrict__ y, i
     sum_ssim += valid ? ssim : 0.0;
     sum_cs += valid ? cs : 0.0;
   }
-  sum_ssim = wave_sum(sum_ssim);
-  sum_cs = wave_sum(sum_cs);
-  if ((tid & 63) == 0) {
-    red[0][tid >> 6] = sum_ssim;
-    red[1][tid >> 6] = sum_cs;
-  }
-  __syncthreads();
+  const double sums[2] = {sum_ssim, sum_cs};
+  const double s = block_sum<kWaves>(sums);
   if (tid < 2) {
-    double s = 0.0;
-    for (int i = 0; i < kWaves; ++i) s += red[tid][i];
     const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     const size_t n_blk = (size_t)gridDim.x * gridDim.y;
     partial[((size_t)c * n_blk + blk) * 2 + tid] = s;
@@ -212,7 +203,6 @@ __global__ void __launch_bounds__(kThreads)
 frame_reduce_kernel(const float* __restrict__ a, const float* __restrict__ b, long long n_pix,
                     const unsigned char* __restrict__ mask, const float* __restrict__ depth,
                     const float* __restrict__ gt_depth, double* __restrict__ partial) {
-  __shared__ double red[4][kWaves];
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   for (long long p = (long long)blockIdx.x * kThreads + threadIdx.x; p < n_pix; p += (long long)gridDim.x * kThreads) {
     double e = 0.0;
@@ -228,17 +218,8 @@ frame_reduce_kernel(const float* __restrict__ a, const float* __restrict__ b, lo
       if (depth && gt_depth) s[3] += (double)fabsf(depth[p] - gt_depth[p]);
     }
   }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const double t = wave_sum(s[q]);
-    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double t = 0.0;
-    for (int i = 0; i < kWaves; ++i) t += red[threadIdx.x][i];
-    partial[(size_t)blockIdx.x * 4 + threadIdx.x] = t;
-  }
+  const double t = block_sum<kWaves>(s);
+  if (threadIdx.x < 4) partial[(size_t)blockIdx.x * 4 + threadIdx.x] = t;
 }
 
 // out = {psnr, masked_psnr, depth_l1}; count = pixels of the mask
@@ -301,21 +282,34 @@ bool make_pyramid(int H, int W, int levels, Pyramid* pyr) {
 // floats of one image of level l, rounded up to an even count (the next image stays 8-byte aligned)
 inline size_t level_floats(const Pyramid& p, int l) { return (3 * (size_t)p.h[l] * p.w[l] + 1) & ~(size_t)1; }
 
-inline int reduce_blocks(long long n_pix) {
-  const long long b = (n_pix + kThreads - 1) / kThreads;
-  return (int)(b < 1 ? 1 : (b > kReduceBlocks ? kReduceBlocks : b));
+inline int reduce_blocks(long long n_pix) { return capped_blocks(n_pix, kThreads); }
+
+// the pooled images of levels 1.. : x then y of a level, float [3, h_l, w_l] each
+struct LevelImages {
+  float *x[kMaxLevels], *y[kMaxLevels];
+};
+inline LevelImages take_images(Carver& c, const Pyramid& p) {
+  LevelImages m = {};
+  for (int l = 1; l < p.levels; ++l) {
+    m.x[l] = c.take<float>(level_floats(p, l));
+    m.y[l] = c.take<float>(level_floats(p, l));
+  }
+  return m;
 }
+
+// workspace: partials double [sum over levels of 3 * blocks * 2] (level l at pyr.offset[l]) | the images of levels 1..
+struct SsimWs {
+  Carver c;
+  Pyramid pyr;
+  double* partial = c.take<double>(pyr.offset[pyr.levels - 1] + 6 * (size_t)pyr.blocks[pyr.levels - 1]);
+  LevelImages img = take_images(c, pyr);
+};
 
 }  // namespace
 
-// workspace: partials double [sum over levels of 3 * blocks * 2] | levels 1.. of x, then of y: float [3, h_l, w_l] each
 extern "C" size_t glorie_ms_ssim_workspace(int H, int W, int levels) {
   Pyramid pyr;
-  if (!make_pyramid(H, W, levels, &pyr)) return 0;
-  size_t bytes = 0;
-  for (int l = 0; l < levels; ++l) bytes += 6 * (size_t)pyr.blocks[l] * sizeof(double);
-  for (int l = 1; l < levels; ++l) bytes += 2 * level_floats(pyr, l) * sizeof(float);
-  return bytes;
+  return make_pyramid(H, W, levels, &pyr) ? carved_bytes<SsimWs>(pyr) : 0;
 }
 
 extern "C" int glorie_ms_ssim(const float* x, const float* y, int H, int W, int channels_first, int levels,
@@ -332,14 +326,14 @@ extern "C" int glorie_ms_ssim(const float* x, const float* y, int H, int W, int 
     sum += win.g[i];
   }
   for (int i = 0; i < kWin; ++i) win.g[i] /= sum;
-  double* partial = reinterpret_cast<double*>(workspace);
-  float* images = reinterpret_cast<float*>(partial + pyr.offset[levels - 1] + 6LL * pyr.blocks[levels - 1]);
+  const SsimWs ws{Carver(workspace), pyr};
+  double* partial = ws.partial;
   const float *cx = x, *cy = y;
   int hwc = channels_first ? 0 : 1;
   for (int l = 0; l < levels; ++l) {
     const bool last = l == levels - 1;
-    float* nx = last ? nullptr : images;
-    float* ny = last ? nullptr : images + level_floats(pyr, l + 1);
+    float* nx = last ? nullptr : ws.img.x[l + 1];
+    float* ny = last ? nullptr : ws.img.y[l + 1];
     const dim3 grid((pyr.w[l] - (kWin - 1) + kTW - 1) / kTW, (pyr.h[l] - (kWin - 1) + kTH - 1) / kTH, last ? 3 : 6);
     hipLaunchKernelGGL(ms_ssim_level_kernel, grid, dim3(kThreads), 0, st, cx, cy, pyr.h[l], pyr.w[l], hwc, win,
                        partial + pyr.offset[l], nx, ny);
@@ -347,7 +341,6 @@ extern "C" int glorie_ms_ssim(const float* x, const float* y, int H, int W, int 
     if (!last) {
       cx = nx;
       cy = ny;
-      images += 2 * level_floats(pyr, l + 1);
       hwc = 0;
     }
   }

@@ -18,7 +18,7 @@
 //   (an integer atomic for the slot; the depth is a minimum, so the queue's order does not matter) and a second launch
 //   spreads every queued triangle over up to kChunks workgroups.  Depth: atomicMin on the bits of the positive fp32 depth.
 #include <float.h>
-#include "common.hiph"
+#include "compact.hiph"
 
 using namespace glorie;
 
@@ -26,47 +26,19 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kReduceBlocks = 1024;           // cap of the grids of the sum kernels
 constexpr int kSmallBox = 256;                // pixels of a box one lane still walks by itself
 constexpr int kChunks = 64;                   // workgroups one queued triangle is spread over, at most
 constexpr int kChunkPixels = 4 * kThreads;    // pixels per workgroup that justify another one
 constexpr int kSlots = 256;                   // grid.y of the large launch: queued triangles taken in parallel
 constexpr unsigned kInfBits = 0x7f800000u;
 
-inline int reduce_blocks(long long n) {
-  const long long b = (n + kThreads - 1) / kThreads;
-  return (int)(b < 1 ? 1 : (b > kReduceBlocks ? kReduceBlocks : b));
-}
+inline int reduce_blocks(long long n) { return capped_blocks(n, kThreads); }
 
-// Sum of n doubles p[0], p[stride], ... by one wave, in a fixed order (as in metrics.hip): lane i adds its contiguous run
-// of ceil(n / 64) elements in index order, then every lane adds the 64 run sums in lane order
-__device__ __forceinline__ double ordered_sum(const double* __restrict__ p, int n, int stride) {
-  const int lane = threadIdx.x & 63;
-  const int run = (n + 63) / 64;
-  const int j0 = min(n, lane * run), j1 = min(n, j0 + run);
-  double s = 0.0;
-  for (int j = j0; j < j1; ++j) s += p[(size_t)j * stride];
-  double t = 0.0;
-#pragma unroll
-  for (int i = 0; i < 64; ++i) t += __shfl(s, i, 64);
-  return t;
-}
-
-// the N sums of a workgroup's threads -> out[0..N)
+// the N sums of a workgroup's threads -> out[0..N); once per kernel (block_reduce is single use)
 template <int N>
 __device__ __forceinline__ void block_partials(const double (&s)[N], double* __restrict__ out) {
-  __shared__ double red[N][kWaves];
-#pragma unroll
-  for (int q = 0; q < N; ++q) {
-    const double t = wave_sum(s[q]);
-    if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    double t = 0.0;
-    for (int i = 0; i < kWaves; ++i) t += red[threadIdx.x][i];
-    out[threadIdx.x] = t;
-  }
+  const double t = block_sum<kWaves>(s);
+  if (threadIdx.x < N) out[threadIdx.x] = t;
 }
 
 // out[s] = sum over the workgroups of partial[b * n_series + s]; n_blocks == 0 gives zeros
@@ -430,7 +402,6 @@ __global__ void __launch_bounds__(kThreads)
 points_in_view_kernel(const float* __restrict__ points, long long n, const float* __restrict__ w2c, Camera cam, double edge,
                       int* __restrict__ count) {
 #pragma clang fp contract(off)
-  __shared__ int red[kWaves];
   int c = 0;
   for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
     const double x = (double)points[3 * i], y = (double)points[3 * i + 1], z = (double)points[3 * i + 2];
@@ -443,14 +414,8 @@ points_in_view_kernel(const float* __restrict__ points, long long n, const float
       c += (pu > edge && pu < (double)cam.W - edge && pv > edge && pv < (double)cam.H - edge) ? 1 : 0;
     }
   }
-  c = wave_sum(c);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int i = 0; i < kWaves; ++i) t += red[i];
-    if (t) atomicAdd(count, t);
-  }
+  c = block_sum<kWaves>(c);
+  if (threadIdx.x == 0 && c) atomicAdd(count, c);
 }
 
 // ---- depth L1 -------------------------------------------------------------------------------------------------------------
@@ -491,34 +456,43 @@ bool make_camera(float fx, float fy, float cx, float cy, int H, int W, float z_n
   return true;
 }
 
-inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
+// workspace of the area CDF: workgroup totals double [ceil(F / 256)] | out double [2] | bad int [2]
+struct AreaWs {
+  Carver c;
+  int F;
+  double* totals = c.take<double>((F + kThreads - 1) / kThreads);
+  double* out = c.take<double>(2);
+  int* bad = c.take<int>(2);
+};
+
+// workspace of the rasteriser: queue count int [2] | queue int [F]
+struct RasterWs {
+  Carver c;
+  int F;
+  int* queue_count = c.take<int>(2);
+  int* queue = c.take<int>(F);
+};
 
 }  // namespace
 
-// workspace: workgroup totals double [ceil(F / 256)] | out double [2] | bad int [2]
-extern "C" size_t glorie_mesh_area_cdf_workspace(int F) {
-  if (F <= 0) return 0;
-  return ((size_t)((F + kThreads - 1) / kThreads) + 2) * sizeof(double) + 2 * sizeof(int);
-}
+extern "C" size_t glorie_mesh_area_cdf_workspace(int F) { return F <= 0 ? 0 : carved_bytes<AreaWs>(F); }
 
 extern "C" int glorie_mesh_area_cdf(const float* vertices, int V, const int* faces, int F, double* cdf, void* workspace,
                                     double* total_out, void* stream) {
   if (V <= 0 || F <= 0 || !vertices || !faces || !cdf || !workspace || !total_out) return GLORIE_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int blocks = (F + kThreads - 1) / kThreads;
-  double* totals = reinterpret_cast<double*>(workspace);
-  double* out = totals + blocks;
-  int* bad = reinterpret_cast<int*>(out + 2);
-  GLORIE_TRY(check_hip(hipMemsetAsync(bad, 0, 2 * sizeof(int), st)));
-  hipLaunchKernelGGL(area_scan_kernel, dim3(blocks), dim3(kThreads), 0, st, vertices, V, faces, (long long)F, cdf, totals,
-                     bad);
+  const AreaWs w{Carver(workspace), F};
+  GLORIE_TRY(check_hip(hipMemsetAsync(w.bad, 0, 2 * sizeof(int), st)));
+  hipLaunchKernelGGL(area_scan_kernel, dim3(blocks), dim3(kThreads), 0, st, vertices, V, faces, (long long)F, cdf,
+                     w.totals, w.bad);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(area_offsets_kernel, dim3(1), dim3(kThreads), 0, st, totals, blocks);
+  hipLaunchKernelGGL(area_offsets_kernel, dim3(1), dim3(kThreads), 0, st, w.totals, blocks);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(area_add_kernel, dim3(blocks), dim3(kThreads), 0, st, cdf, (long long)F, totals, bad, out);
+  hipLaunchKernelGGL(area_add_kernel, dim3(blocks), dim3(kThreads), 0, st, cdf, (long long)F, w.totals, w.bad, w.out);
   GLORIE_TRY(check_launch());
   double host[2] = {0.0, 0.0};
-  GLORIE_TRY(check_hip(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, st)));
+  GLORIE_TRY(check_hip(hipMemcpyAsync(host, w.out, sizeof(host), hipMemcpyDeviceToHost, st)));
   GLORIE_TRY(check_hip(hipStreamSynchronize(st)));
   *total_out = host[0];
   return host[1] != 0.0 ? GLORIE_EINVAL : GLORIE_OK;
@@ -581,11 +555,7 @@ extern "C" int glorie_nn_stats(const float* D, int Q, float threshold, void* wor
   return check_launch();
 }
 
-// workspace: queue count int [2] | queue int [F]
-extern "C" size_t glorie_mesh_depth_workspace(int F) {
-  if (F <= 0) return 0;
-  return align8(((size_t)F + 2) * sizeof(int));
-}
+extern "C" size_t glorie_mesh_depth_workspace(int F) { return F <= 0 ? 0 : carved_bytes<RasterWs>(F); }
 
 extern "C" int glorie_mesh_depth(const float* vertices, int V, const int* faces, int F, const float* w2c, float fx, float fy,
                                  float cx, float cy, int H, int W, float z_near, float z_far, int policy, void* workspace,
@@ -597,16 +567,16 @@ extern "C" int glorie_mesh_depth(const float* vertices, int V, const int* faces,
   hipStream_t st = (hipStream_t)stream;
   const long long n_pix = (long long)H * W;
   if (F > 0) {
-    int* queue_count = reinterpret_cast<int*>(workspace);
-    hipLaunchKernelGGL(raster_fill_kernel, dim3(reduce_blocks(n_pix)), dim3(kThreads), 0, st, depth_bits, n_pix, queue_count);
+    const RasterWs w{Carver(workspace), F};
+    hipLaunchKernelGGL(raster_fill_kernel, dim3(reduce_blocks(n_pix)), dim3(kThreads), 0, st, depth_bits, n_pix,
+                       w.queue_count);
     GLORIE_TRY(check_launch());
-    int* queue = queue_count + 2;
     hipLaunchKernelGGL(raster_small_kernel, dim3((F + kThreads - 1) / kThreads), dim3(kThreads), 0, st, vertices, V, faces, F,
-                       w2c, cam, policy, depth_bits, queue_count, queue);
+                       w2c, cam, policy, depth_bits, w.queue_count, w.queue);
     GLORIE_TRY(check_launch());
     if (policy != 1) {
       hipLaunchKernelGGL(raster_large_kernel, dim3(kChunks, F < kSlots ? F : kSlots), dim3(kThreads), 0, st, vertices, V,
-                         faces, F, w2c, cam, depth_bits, queue_count, queue);
+                         faces, F, w2c, cam, depth_bits, w.queue_count, w.queue);
       GLORIE_TRY(check_launch());
     }
     hipLaunchKernelGGL(raster_resolve_kernel, dim3(reduce_blocks(n_pix)), dim3(kThreads), 0, st, depth_bits, n_pix, depth);

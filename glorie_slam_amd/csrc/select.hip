@@ -14,7 +14,7 @@
 //                           (an integer atomic max on an order-preserving key of the float: exact in any order)
 //   frustum_mask_kernel     sampled depth 0 -> that maximum (`depths[zero_mask] = np.max(depths)`), keep when
 //                           0 <= -z <= depth + 0.5; one kept count per workgroup (wave ballots, no atomics)
-//   select_scan_kernel      one workgroup: exclusive scan of the workgroup counts -> offsets and the total count
+//   exclusive_scan_kernel   one workgroup: exclusive scan of the workgroup counts -> offsets and the total count
 //   frustum_indices_kernel  (only when indices are asked for) the kept points' indices in ascending order
 // The count, scan and rank steps are those of compact.hiph.
 // Overlap count, one launch: overlap_count_kernel, one workgroup per keyframe, an integer sum over the ray samples.
@@ -51,7 +51,6 @@ __global__ void __launch_bounds__(kSelThreads)
 frustum_sample_kernel(const float* __restrict__ points, int n, const float* __restrict__ c2w, float fx, float fy,
                       float cx, float cy, int H, int W, float edge, const float* __restrict__ depth,
                       float2* __restrict__ zd, unsigned int* __restrict__ max_key) {
-  __shared__ unsigned int red[kSelWaves];
   const Rigid w = rigid_inverse(c2w);
   const int i = blockIdx.x * kSelThreads + threadIdx.x;
   unsigned int key = 0;
@@ -63,14 +62,8 @@ frustum_sample_kernel(const float* __restrict__ points, int n, const float* __re
     key = float_key(s);
   }
   // workgroup maximum, then one atomic per workgroup
-  key = wave_max(key);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned int m = red[0];
-    for (int k = 1; k < kSelWaves; ++k) m = max(m, red[k]);
-    atomicMax(max_key, m);
-  }
+  key = block_max<kSelWaves>(key);
+  if (threadIdx.x == 0) atomicMax(max_key, key);
 }
 
 __global__ void __launch_bounds__(kSelThreads)
@@ -91,16 +84,6 @@ frustum_mask_kernel(const float2* __restrict__ zd, int n, const unsigned int* __
   if (threadIdx.x == 0) block_count[blockIdx.x] = slot_sum(red, kSelWaves);
 }
 
-// one workgroup: offsets[b] = sum of counts[0, b), total[0] = sum of all
-__global__ void __launch_bounds__(kScanThreads)
-select_scan_kernel(const int* __restrict__ counts, int n_blocks, int* __restrict__ offsets, int* __restrict__ total) {
-  const int* const in[1] = {counts};
-  int* const out[1] = {offsets};
-  int sum[1];
-  block_exclusive_scan<1>(in, out, n_blocks, sum);
-  if (threadIdx.x == 0) total[0] = sum[0];
-}
-
 __global__ void __launch_bounds__(kSelThreads)
 frustum_indices_kernel(const unsigned char* __restrict__ mask, int n, const int* __restrict__ offsets,
                        int64_t* __restrict__ indices) {
@@ -118,7 +101,6 @@ __global__ void __launch_bounds__(kSelThreads)
 overlap_count_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                      const float* __restrict__ depth, int R, int n_samples, const float* __restrict__ c2ws, float fx,
                      float fy, float cx, float cy, int H, int W, float edge, int* __restrict__ inside) {
-  __shared__ int red[kSelWaves];
   const Rigid w = rigid_inverse(c2ws + 16 * (size_t)blockIdx.x);
   const int total = R * n_samples;
   const float step = n_samples > 1 ? 1.f / (float)(n_samples - 1) : 0.f;
@@ -135,23 +117,39 @@ overlap_count_kernel(const float* __restrict__ rays_o, const float* __restrict__
                            rays_o[3 * r + 2] + rays_d[3 * r + 2] * zs, fx, fy, cx, cy, kProjEps);
     count += (inside_edge(p.u, p.v, H, W, edge) && p.z < 0.f) ? 1 : 0;
   }
-  count = wave_sum(count);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = count;
-  __syncthreads();
-  if (threadIdx.x == 0) inside[blockIdx.x] = slot_sum(red, kSelWaves);
+  count = block_sum<kSelWaves>(count);
+  if (threadIdx.x == 0) inside[blockIdx.x] = count;
 }
 
 inline int sel_blocks(int n) { return (n + kSelThreads - 1) / kSelThreads; }
 
+// workspace layout: zd float2 [n] | block counts int [B] | offsets int [B] | max key uint (8-byte aligned pieces)
+struct FrustumWs {
+  Carver c;
+  int n;
+  float2* zd = c.take<float2>(n);
+  int* block_count = c.take<int>(sel_blocks(n));
+  int* offsets = c.take<int>(sel_blocks(n));
+  unsigned int* max_key = c.take<unsigned int>(1);
+};
+
+__global__ void __launch_bounds__(kScanThreads)
+exclusive_scan_kernel(const int* __restrict__ counts, int n, int* __restrict__ offsets, int* __restrict__ total) {
+  const int* const in[1] = {counts};
+  int* const out[1] = {offsets};
+  int sum[1];
+  block_exclusive_scan<1>(in, out, n, sum);
+  if (total && threadIdx.x == 0) total[0] = sum[0];
+}
+
 }  // namespace
 
-// workspace layout: zd float2 [n] | block counts int [B] | offsets int [B] | max key uint (8-byte aligned pieces)
-
-extern "C" size_t glorie_frustum_select_workspace(int n) {
-  if (n < 0) return 0;
-  const size_t B = (size_t)sel_blocks(n);
-  return align8((size_t)n * sizeof(float2)) + 2 * align8(B * sizeof(int)) + 8;
+int glorie::launch_exclusive_scan(const int* counts, int n, int* offsets, int* total, hipStream_t st) {
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, counts, n, offsets, total);
+  return check_launch();
 }
+
+extern "C" size_t glorie_frustum_select_workspace(int n) { return n < 0 ? 0 : carved_bytes<FrustumWs>(n); }
 
 extern "C" int glorie_frustum_select(const float* points, int n, const float* c2w, float fx, float fy, float cx,
                                      float cy, int H, int W, float edge, const float* depth, void* workspace,
@@ -161,22 +159,16 @@ extern "C" int glorie_frustum_select(const float* points, int n, const float* c2
   if (n == 0) return check_hip(hipMemsetAsync(count, 0, sizeof(int), st));
   if (!points || !c2w || !depth || !workspace || !mask) return GLORIE_EINVAL;
   const int B = sel_blocks(n);
-  char* ws = reinterpret_cast<char*>(workspace);
-  float2* zd = reinterpret_cast<float2*>(ws);
-  int* block_count = reinterpret_cast<int*>(ws + align8((size_t)n * sizeof(float2)));
-  int* offsets = reinterpret_cast<int*>(reinterpret_cast<char*>(block_count) + align8((size_t)B * sizeof(int)));
-  unsigned int* max_key = reinterpret_cast<unsigned int*>(reinterpret_cast<char*>(offsets) +
-                                                          align8((size_t)B * sizeof(int)));
-  GLORIE_TRY(check_hip(hipMemsetAsync(max_key, 0, sizeof(unsigned int), st)));
+  const FrustumWs w{Carver(workspace), n};
+  GLORIE_TRY(check_hip(hipMemsetAsync(w.max_key, 0, sizeof(unsigned int), st)));
   hipLaunchKernelGGL(frustum_sample_kernel, dim3(B), dim3(kSelThreads), 0, st, points, n, c2w, fx, fy, cx, cy, H, W,
-                     edge, depth, zd, max_key);
+                     edge, depth, w.zd, w.max_key);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(frustum_mask_kernel, dim3(B), dim3(kSelThreads), 0, st, zd, n, max_key, mask, block_count);
+  hipLaunchKernelGGL(frustum_mask_kernel, dim3(B), dim3(kSelThreads), 0, st, w.zd, n, w.max_key, mask, w.block_count);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, block_count, B, offsets, count);
-  GLORIE_TRY(check_launch());
+  GLORIE_TRY(launch_exclusive_scan(w.block_count, B, w.offsets, count, st));
   if (indices) {
-    hipLaunchKernelGGL(frustum_indices_kernel, dim3(B), dim3(kSelThreads), 0, st, mask, n, offsets, indices);
+    hipLaunchKernelGGL(frustum_indices_kernel, dim3(B), dim3(kSelThreads), 0, st, mask, n, w.offsets, indices);
     GLORIE_TRY(check_launch());
   }
   return GLORIE_OK;

@@ -24,7 +24,8 @@
 //                        (V, F) go to the workspace
 //   tsdf_bases_kernel    exclusive scan of the per-block counts
 //   tsdf_emit_kernel     recomputes the cell results and writes vertices, colours and faces at their canonical places
-// The scans are block_exclusive_scan of compact.hiph.  Only integer atomics (two statistics counters): repeated runs
+// The scans are block_exclusive_scan of compact.hiph; the one-array scan of the block order is launch_exclusive_scan, whose
+// kernel is defined in select.hip (this file needs it linked, as libglorie_hip.so does).  Only integer atomics (two statistics counters): repeated runs
 // are bitwise equal.
 #include "compact.hiph"
 
@@ -341,14 +342,6 @@ tsdf_order_count_kernel(const int* __restrict__ table, int n_table, int* __restr
   if (threadIdx.x == 0) wg_count[blockIdx.x] = slot_sum(red, kWaves);
 }
 
-__global__ void __launch_bounds__(kScanThreads)
-tsdf_scan1_kernel(const int* __restrict__ in0, int n, int* __restrict__ out0) {
-  const int* const in[1] = {in0};
-  int* const out[1] = {out0};
-  int sum[1];
-  block_exclusive_scan<1>(in, out, n, sum);
-}
-
 // order[r] = table index of the r-th allocated block in ascending table index; rank_of[id] = r
 __global__ void __launch_bounds__(kThreads)
 tsdf_order_rank_kernel(const int* __restrict__ table, int n_table, const int* __restrict__ wg_offset, int n_blocks,
@@ -502,44 +495,40 @@ inline Grid make_grid(const float* origin, float vl, const int* nb) {
   return Grid{origin[0], origin[1], origin[2], vl, nb[0], nb[1], nb[2]};
 }
 
+// workspace of the extraction: per table workgroup B = wgs(n_table), per allocated block n (at least one)
 struct ExtractWs {
-  int *wg_count, *wg_offset, *order, *rank_of, *block_v, *block_f, *base_v, *base_f, *totals;
-  unsigned short* cell_prefix;
-  unsigned char* cell_mask;
-  size_t bytes;
+  Carver c;
+  long long n_table;
+  int n_blocks;
+  size_t B = (size_t)wgs(n_table), n = (size_t)(n_blocks > 0 ? n_blocks : 1);
+  int* wg_count = c.take<int>(B);
+  int* wg_offset = c.take<int>(B);
+  int* order = c.take<int>(n);
+  int* rank_of = c.take<int>(n);
+  int* block_v = c.take<int>(n);
+  int* block_f = c.take<int>(n);
+  int* base_v = c.take<int>(n);
+  int* base_f = c.take<int>(n);
+  int* totals = c.take<int>(2);
+  unsigned short* cell_prefix = c.take<unsigned short>(n * kVox);
+  unsigned char* cell_mask = c.take<unsigned char>(n * kVox);
 };
 
-inline ExtractWs carve_extract(void* workspace, long long n_table, int n_blocks) {
-  ExtractWs w;
-  char* p = reinterpret_cast<char*>(workspace);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* q = p ? p + off : nullptr;
-    off += align8(bytes);
-    return q;
-  };
-  const size_t B = (size_t)wgs(n_table), n = (size_t)(n_blocks > 0 ? n_blocks : 1);
-  w.wg_count = reinterpret_cast<int*>(take(B * sizeof(int)));
-  w.wg_offset = reinterpret_cast<int*>(take(B * sizeof(int)));
-  w.order = reinterpret_cast<int*>(take(n * sizeof(int)));
-  w.rank_of = reinterpret_cast<int*>(take(n * sizeof(int)));
-  w.block_v = reinterpret_cast<int*>(take(n * sizeof(int)));
-  w.block_f = reinterpret_cast<int*>(take(n * sizeof(int)));
-  w.base_v = reinterpret_cast<int*>(take(n * sizeof(int)));
-  w.base_f = reinterpret_cast<int*>(take(n * sizeof(int)));
-  w.totals = reinterpret_cast<int*>(take(2 * sizeof(int)));
-  w.cell_prefix = reinterpret_cast<unsigned short*>(take(n * kVox * sizeof(unsigned short)));
-  w.cell_mask = reinterpret_cast<unsigned char*>(take(n * kVox));
-  w.bytes = off;
-  return w;
-}
+// workspace of the allocation: flags u8 [n_table] | workgroup counts int [B] | offsets int [B] | admit int [2]
+struct AllocateWs {
+  Carver c;
+  long long n_table;
+  unsigned char* flag = c.take<unsigned char>((size_t)n_table);
+  int* wg_count = c.take<int>((size_t)wgs(n_table));
+  int* wg_offset = c.take<int>((size_t)wgs(n_table));
+  int* admit = c.take<int>(2);
+};
 
 }  // namespace
 
-// workspace: flags u8 [n_table] | workgroup counts int [B] | offsets int [B] | admit int [2]
 extern "C" size_t glorie_tsdf_allocate_workspace(long n_table) {
   if (n_table <= 0 || n_table > 0x7fffffffLL - kThreads) return 0;
-  return align8((size_t)n_table) + 2 * align8((size_t)wgs(n_table) * sizeof(int)) + 8;
+  return carved_bytes<AllocateWs>((long long)n_table);
 }
 
 extern "C" int glorie_tsdf_allocate(const float* depth, int H, int W, const float* c2w, float fx, float fy, float cx,
@@ -554,21 +543,17 @@ extern "C" int glorie_tsdf_allocate(const float* depth, int H, int W, const floa
   const Cam cam{fx, fy, cx, cy, H, W};
   const int n_table = blocks_per_axis[0] * blocks_per_axis[1] * blocks_per_axis[2];
   const int B = wgs(n_table);
-  char* ws = reinterpret_cast<char*>(workspace);
-  unsigned char* flag = reinterpret_cast<unsigned char*>(ws);
-  int* wg_count = reinterpret_cast<int*>(ws + align8((size_t)n_table));
-  int* wg_offset = reinterpret_cast<int*>(reinterpret_cast<char*>(wg_count) + align8((size_t)B * sizeof(int)));
-  int* admit = reinterpret_cast<int*>(reinterpret_cast<char*>(wg_offset) + align8((size_t)B * sizeof(int)));
-  GLORIE_TRY(check_hip(hipMemsetAsync(flag, 0, (size_t)n_table, st)));
+  const AllocateWs w{Carver(workspace), n_table};
+  GLORIE_TRY(check_hip(hipMemsetAsync(w.flag, 0, (size_t)n_table, st)));
   hipLaunchKernelGGL(tsdf_flag_kernel, dim3(wgs((long long)H * W)), dim3(kThreads), 0, st, depth, cam, c2w, depth_trunc,
-                     sdf_trunc, g, flag, counters);
+                     sdf_trunc, g, w.flag, counters);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(tsdf_new_kernel, dim3(B), dim3(kThreads), 0, st, flag, table, n_table, wg_count);
+  hipLaunchKernelGGL(tsdf_new_kernel, dim3(B), dim3(kThreads), 0, st, w.flag, table, n_table, w.wg_count);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(tsdf_admit_kernel, dim3(1), dim3(kScanThreads), 0, st, wg_count, B, wg_offset, max_blocks, counters,
-                     admit);
+  hipLaunchKernelGGL(tsdf_admit_kernel, dim3(1), dim3(kScanThreads), 0, st, w.wg_count, B, w.wg_offset, max_blocks,
+                     counters, w.admit);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(tsdf_assign_kernel, dim3(B), dim3(kThreads), 0, st, flag, table, n_table, wg_offset, admit,
+  hipLaunchKernelGGL(tsdf_assign_kernel, dim3(B), dim3(kThreads), 0, st, w.flag, table, n_table, w.wg_offset, w.admit,
                      block_index);
   GLORIE_TRY(check_launch());
   int host[3] = {0, 0, 0};                                        // blocks in use, pixels outside, refused
@@ -598,7 +583,7 @@ extern "C" int glorie_tsdf_integrate(const float* depth, const float* color, int
 
 extern "C" size_t glorie_tsdf_extract_workspace(long n_table, int n_blocks) {
   if (n_table <= 0 || n_table > 0x7fffffffLL - kThreads || n_blocks < 0) return 0;
-  return carve_extract(nullptr, n_table, n_blocks).bytes;
+  return carved_bytes<ExtractWs>((long long)n_table, n_blocks);
 }
 
 extern "C" int glorie_tsdf_extract_count(const float* origin, float voxel_length, const int* blocks_per_axis,
@@ -613,11 +598,10 @@ extern "C" int glorie_tsdf_extract_count(const float* origin, float voxel_length
   const Grid g = make_grid(origin, voxel_length, blocks_per_axis);
   const int n_table = blocks_per_axis[0] * blocks_per_axis[1] * blocks_per_axis[2];
   const int B = wgs(n_table);
-  const ExtractWs w = carve_extract(workspace, n_table, n_blocks);
+  const ExtractWs w{Carver(workspace), n_table, n_blocks};
   hipLaunchKernelGGL(tsdf_order_count_kernel, dim3(B), dim3(kThreads), 0, st, table, n_table, w.wg_count);
   GLORIE_TRY(check_launch());
-  hipLaunchKernelGGL(tsdf_scan1_kernel, dim3(1), dim3(kScanThreads), 0, st, w.wg_count, B, w.wg_offset);
-  GLORIE_TRY(check_launch());
+  GLORIE_TRY(launch_exclusive_scan(w.wg_count, B, w.wg_offset, nullptr, st));
   hipLaunchKernelGGL(tsdf_order_rank_kernel, dim3(B), dim3(kThreads), 0, st, table, n_table, w.wg_offset, n_blocks,
                      w.order, w.rank_of);
   GLORIE_TRY(check_launch());
@@ -643,7 +627,7 @@ extern "C" int glorie_tsdf_extract_emit(const double* origin, double voxel_lengt
   const Grid g = make_grid(origin_f, (float)voxel_length, blocks_per_axis);
   const GridD gd{origin[0], origin[1], origin[2], voxel_length};
   const int n_table = blocks_per_axis[0] * blocks_per_axis[1] * blocks_per_axis[2];
-  const ExtractWs w = carve_extract(workspace, n_table, n_blocks);
+  const ExtractWs w{Carver(workspace), n_table, n_blocks};
   hipLaunchKernelGGL(tsdf_emit_kernel, dim3(n_blocks), dim3(kVox), 0, (hipStream_t)stream, g, gd, table, tsdf, weight,
                      rgb, w.order, w.rank_of, w.cell_mask, w.cell_prefix, w.base_v, w.base_f, vertices, colors, faces);
   return check_launch();

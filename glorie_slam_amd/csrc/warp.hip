@@ -12,7 +12,7 @@
 // gradient scale 1 / (3 count), both on the device), pix_warp_bwd_kernel (grad_depth = raw * g_out * scale).  No atomics:
 // repeated calls are bitwise identical, and nothing the host sizes depends on the data (the term records into a hipGraph).
 #include "camera.hiph"
-#include "common.hiph"
+#include "compact.hiph"
 
 using namespace glorie;
 
@@ -189,12 +189,17 @@ __global__ void pix_warp_bwd_kernel(const float* __restrict__ raw_grad, const fl
 
 inline int warp_parts(int N) { return (N + kWarpThreads - 1) / kWarpThreads; }
 
+// workspace: per-workgroup loss double [parts] | kept count long long [parts]
+struct WarpWs {
+  Carver c;
+  int parts;
+  double* part_loss = c.take<double>(parts);
+  long long* part_count = c.take<long long>(parts);
+};
+
 }  // namespace
 
-extern "C" size_t glorie_pix_warp_workspace(int N) {
-  if (N < 0) return 0;
-  return (size_t)warp_parts(N) * (sizeof(double) + sizeof(long long));
-}
+extern "C" size_t glorie_pix_warp_workspace(int N) { return N < 0 ? 0 : carved_bytes<WarpWs>(warp_parts(N)); }
 
 extern "C" int glorie_pix_warp_fwd(const float* rays_o, const float* rays_d, const float* depth, const int64_t* ray_frame,
                                    int N, const float* c2ws, const int64_t* frame_indices, int M, const float* images,
@@ -204,19 +209,18 @@ extern "C" int glorie_pix_warp_fwd(const float* rays_o, const float* rays_d, con
   if (N < 0 || M < 0 || M > kWarpMaxFrames || H <= 2 * kWarpEdge || W <= 2 * kWarpEdge) return GLORIE_EINVAL;
   if (!loss || !scale) return GLORIE_EINVAL;
   const int parts = warp_parts(N);
-  double* part_loss = reinterpret_cast<double*>(workspace);
-  long long* part_count = reinterpret_cast<long long*>(part_loss + parts);
+  const WarpWs w{Carver(workspace), parts};
   if (N > 0) {
     if (!rays_o || !rays_d || !depth || !ray_frame || !gt_color || !raw_grad || !workspace) return GLORIE_EINVAL;
     if (M > 0 && (!c2ws || !frame_indices || (!images && !frame_table))) return GLORIE_EINVAL;
     hipLaunchKernelGGL(pix_warp_fwd_kernel, dim3(parts), dim3(kWarpThreads), 0, (hipStream_t)stream, rays_o, rays_d,
                        depth, ray_frame, N, c2ws, frame_indices, M, images,
-                       reinterpret_cast<const float* const*>(frame_table), chw, H, W, fx, fy, cx, cy, gt_color, part_loss,
-                       part_count, raw_grad);
+                       reinterpret_cast<const float* const*>(frame_table), chw, H, W, fx, fy, cx, cy, gt_color,
+                       w.part_loss, w.part_count, raw_grad);
     GLORIE_TRY(check_launch());
   }
-  hipLaunchKernelGGL(pix_warp_finish_kernel, dim3(1), dim3(kWarpThreads), 0, (hipStream_t)stream, part_loss, part_count,
-                     N > 0 ? parts : 0, nan_to_zero, loss, scale, count);
+  hipLaunchKernelGGL(pix_warp_finish_kernel, dim3(1), dim3(kWarpThreads), 0, (hipStream_t)stream, w.part_loss,
+                     w.part_count, N > 0 ? parts : 0, nan_to_zero, loss, scale, count);
   return check_launch();
 }
 
