@@ -156,6 +156,40 @@ __global__ __launch_bounds__(256) void frame_distance_kernel(
 }
 
 // ------------------------------------------------------------------------------------
+// projmap (src/lib/droid_kernels.cu:427-516): the projection of frame ii[n] into frame jj[n] with ONE set of
+// intrinsics; where Z <= 0.01 the coordinate is the pixel grid itself, valid = Z > 0.25 (MIN_DEPTH of the native
+// kernels).  Not reproject_kernel: other thresholds, a grid fallback, no stereo edge.  grid (ceil(HW/256), N)
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void projmap_kernel(
+    const float* __restrict__ poses, const float* __restrict__ disps, const float* __restrict__ intr,
+    const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, float* __restrict__ coords,
+    float* __restrict__ valid, int h, int w) {
+  const int n = blockIdx.y;
+  const int HW = h * w;
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  const int ix = static_cast<int>(ii[n]);
+  const int jx = static_cast<int>(jj[n]);
+  const float fx = intr[0], fy = intr[1], cx = intr[2], cy = intr[3];
+  const Pose gij = relative_pose(load_pose(poses + ix * 7), load_pose(poses + jx * 7));
+  if (k >= HW) return;
+  const int y = k / w, x = k - y * w;
+  const float u = (float)x, v = (float)y;
+  float Xi[4], Xj[4];
+  Xi[0] = (u - cx) / fx;
+  Xi[1] = (v - cy) / fy;
+  Xi[2] = 1.0f;
+  Xi[3] = disps[(size_t)ix * HW + k];
+  se3_act(gij, Xi, Xj);
+  float2 c = make_float2(u, v);
+  if (Xj[2] > 0.01f) {
+    c.x = fx * (Xj[0] / Xj[2]) + cx;
+    c.y = fy * (Xj[1] / Xj[2]) + cy;
+  }
+  reinterpret_cast<float2*>(coords)[(size_t)n * HW + k] = c;
+  valid[(size_t)n * HW + k] = (Xj[2] > 0.25f) ? 1.0f : 0.0f;
+}
+
+// ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void iproj_kernel(
     const float* __restrict__ poses, const float* __restrict__ disps,
     const float* __restrict__ intr, float* __restrict__ points, int h, int w) {
@@ -421,6 +455,18 @@ extern "C" int glorie_reproject_motion(const float* poses, const float* disps, c
   hipLaunchKernelGGL(reproject_kernel, grid, dim3(256), 0, (hipStream_t)stream, poses, disps, intrinsics, ii, jj, coords,
                      valid, h, w, reinterpret_cast<const float2*>(target), reinterpret_cast<_Float16*>(padded_motion),
                      limit);
+  return check_launch();
+}
+
+extern "C" int glorie_projmap(const float* poses, const float* disps, const float* intrinsics, const int64_t* ii,
+                              const int64_t* jj, float* coords, float* valid, int N, int h, int w, void* stream) {
+  if (N < 0 || h < 0 || w < 0) return GLORIE_EINVAL;
+  if (N == 0 || h * w == 0) return GLORIE_OK;
+  if (N > 65535) return GLORIE_EUNSUPPORTED;
+  if (!poses || !disps || !intrinsics || !ii || !jj || !coords || !valid) return GLORIE_EINVAL;
+  dim3 grid((h * w + 255) / 256, N);
+  hipLaunchKernelGGL(projmap_kernel, grid, dim3(256), 0, (hipStream_t)stream, poses, disps, intrinsics, ii, jj, coords,
+                     valid, h, w);
   return check_launch();
 }
 

@@ -3,11 +3,12 @@
 
 Same function names, argument order, return shapes and error behaviour (non-contiguous
 input -> RuntimeError, like CHECK_CONTIGUOUS at droid.cpp:85-86).  ``ba`` mutates ``poses``
-and ``disps`` in place exactly like ``ba_cuda``.  The backward ops and ``projmap`` are not on
-the inference hot path and raise NotImplementedError.
+and ``disps`` in place exactly like ``ba_cuda``.  All nine names of the extension are implemented; the backward
+ops (``corr_index_backward``, ``altcorr_backward``: csrc/corr_bwd.hip) and ``projmap`` are not on the inference hot
+path but are what the autograd functions of droid_net.py call.
 
 Extra entry points (fused forms the reference builds out of several torch ops):
-``corr_lookup_pyramid``, ``reproject``, ``cvx_upsample``.
+``corr_lookup_pyramid``, ``corr_lookup_pyramid_backward``, ``reproject``, ``cvx_upsample``.
 """
 import ctypes
 import os
@@ -225,8 +226,46 @@ def cl_to_planar(cl):
 
 
 def corr_index_backward(volume, coords, corr_grad, radius):
-    raise NotImplementedError("corr_index_backward: training-only; the SLAM hot path runs under "
-                              "no_grad (factor_graph.py:213)")
+    """volume [N,h1,w1,h2,w2] (f16|f32; only its shape and dtype are used), coords [N,2,h1,w1] f32, corr_grad
+    [N,2r+1,2r+1,h1,w1] of the volume's dtype -> [volume_grad [N,h1,w1,h2,w2]]: the adjoint of corr_index_forward, every
+    element written by the launch (no zero fill).  reference: droid.cpp:182-193, correlation_kernels.cu:73-124,157-185"""
+    L.need_cuda(volume, coords, corr_grad)
+    L.need_contiguous(volume=volume, coords=coords, corr_grad=corr_grad)
+    if coords.dtype != torch.float32:
+        raise RuntimeError("coords must be float32")
+    if corr_grad.dtype != volume.dtype:
+        raise RuntimeError("corr_grad must have the dtype of volume")
+    N, h1, w1, h2, w2 = volume.shape
+    rd = 2 * radius + 1
+    if corr_grad.numel() != N * rd * rd * h1 * w1 or tuple(coords.shape) != (N, 2, h1, w1):
+        raise RuntimeError(f"corr_grad {tuple(corr_grad.shape)} / coords {tuple(coords.shape)} do not match the volume")
+    volume_grad = torch.empty_like(volume)
+    L.check(L.load().glorie_corr_index_bwd(L.ptr(coords), L.ptr(corr_grad), L.ptr(volume_grad), N, h1, w1, h2, w2,
+                                           radius, L.dtype_code(volume), L.stream_ptr()), "glorie_corr_index_bwd")
+    return [volume_grad]
+
+
+def corr_lookup_pyramid_backward(pyramid_shapes, coords, grad, radius):
+    """Adjoint of corr_lookup_pyramid in one launch: pyramid_shapes = the level shapes [(N,h1,w1,h2>>l,w2>>l)], coords
+    [N,2,h1,w1] f32 UNscaled, grad [N, L*(2r+1)^2, h1, w1] (f16|f32) -> list of level gradients of grad's dtype"""
+    L.need_cuda(coords, grad)
+    L.need_contiguous(coords=coords, grad=grad)
+    if coords.dtype != torch.float32:
+        raise RuntimeError("coords must be float32")
+    N, h1, w1, h2, w2 = pyramid_shapes[0]
+    nl = len(pyramid_shapes)
+    rd = 2 * radius + 1
+    for l, shp in enumerate(pyramid_shapes):
+        if tuple(shp) != (N, h1, w1, h2 >> l, w2 >> l):
+            raise RuntimeError(f"pyramid level {l} has shape {tuple(shp)}")
+    if tuple(grad.shape) != (N, nl * rd * rd, h1, w1) or tuple(coords.shape) != (N, 2, h1, w1):
+        raise RuntimeError(f"grad {tuple(grad.shape)} / coords {tuple(coords.shape)} do not match the pyramid")
+    grads = [torch.empty(tuple(shp), dtype=grad.dtype, device=grad.device) for shp in pyramid_shapes]
+    arr = (ctypes.c_void_p * nl)(*[v.data_ptr() for v in grads])
+    L.check(L.load().glorie_corr_lookup_pyramid_bwd(L.ptr(coords), L.ptr(grad), ctypes.cast(arr, ctypes.c_void_p), nl, N,
+                                                    h1, w1, h2, w2, radius, L.dtype_code(grad), L.stream_ptr()),
+            "glorie_corr_lookup_pyramid_bwd")
+    return grads
 
 
 def altcorr_forward(fmap1, fmap2, coords, radius):
@@ -248,7 +287,27 @@ def altcorr_forward(fmap1, fmap2, coords, radius):
 
 
 def altcorr_backward(fmap1, fmap2, coords, corr_grad, radius):
-    raise NotImplementedError("altcorr_backward: training-only, not on the SLAM hot path")
+    """fmap1 [B,H,W,C], fmap2 [B,H2,W2,C], coords [B,S,H,W,2], corr_grad [B,S,(2r+1)^2,H,W] (all f32) ->
+    [fmap1_grad, fmap2_grad, coords_grad]; coords_grad is a zero tensor (coordinates get no gradient), fmap2_grad is summed
+    with float atomics (not bitwise repeatable on general data).  reference: droid.cpp:207-219, altcorr_kernel.cu:153-286,321-356"""
+    L.need_cuda(fmap1, fmap2, coords, corr_grad)
+    L.need_contiguous(fmap1=fmap1, fmap2=fmap2, coords=coords, corr_grad=corr_grad)
+    if any(t.dtype != torch.float32 for t in (fmap1, fmap2, coords, corr_grad)):
+        raise RuntimeError("altcorr_backward takes float32 tensors (corr.py:125 casts)")
+    B, H, W, C = fmap1.shape
+    _, H2, W2, _ = fmap2.shape
+    S = coords.shape[1]
+    rd = 2 * radius + 1
+    if tuple(coords.shape) != (B, S, H, W, 2) or corr_grad.numel() != B * S * rd * rd * H * W \
+            or fmap2.shape[0] != B or fmap2.shape[3] != C:
+        raise RuntimeError("altcorr_backward: shape mismatch")
+    fmap1_grad = torch.empty_like(fmap1)
+    fmap2_grad = torch.zeros_like(fmap2)
+    coords_grad = torch.zeros_like(coords)
+    L.check(L.load().glorie_altcorr_bwd(L.ptr(fmap1), L.ptr(fmap2), L.ptr(coords), L.ptr(corr_grad), L.ptr(fmap1_grad),
+                                        L.ptr(fmap2_grad), B, S, H, W, H2, W2, C, radius, L.stream_ptr()),
+            "glorie_altcorr_bwd")
+    return [fmap1_grad, fmap2_grad, coords_grad]
 
 
 # --------------------------------------------------------------------------------------
@@ -269,8 +328,22 @@ def frame_distance(poses, disps, intrinsics, ii, jj, beta):
 
 
 def projmap(poses, disps, intrinsics, ii, jj):
-    raise NotImplementedError("projmap is exported by the reference but never called "
-                              "(SURVEY.md section 2.1)")
+    """poses [B,7], disps [B,h,w], intrinsics [4], ii/jj [N] int64 -> [coords [N,h,w,2], valid [N,h,w,1]]: the pixel grid
+    where Z <= 0.01, the projection otherwise; valid = Z > 0.25.  reference: droid.cpp:141-156, droid_kernels.cu:427-516"""
+    L.need_cuda(poses, disps, intrinsics, ii, jj)
+    L.need_contiguous(poses=poses, disps=disps, intrinsics=intrinsics, ii=ii, jj=jj)
+    _i64(ii, "ii"), _i64(jj, "jj")
+    if poses.dtype != torch.float32 or disps.dtype != torch.float32 or intrinsics.dtype != torch.float32:
+        raise RuntimeError("projmap takes float32 poses, disps and intrinsics")
+    if intrinsics.numel() < 4 or jj.shape != ii.shape:
+        raise RuntimeError("projmap: intrinsics [4] and edge lists of one length expected")
+    N = ii.shape[0]
+    h, w = disps.shape[1:]
+    coords = torch.empty((N, h, w, 2), dtype=torch.float32, device=poses.device)
+    valid = torch.empty((N, h, w, 1), dtype=torch.float32, device=poses.device)
+    L.check(L.load().glorie_projmap(L.ptr(poses), L.ptr(disps), L.ptr(intrinsics), L.ptr(ii), L.ptr(jj), L.ptr(coords),
+                                    L.ptr(valid), N, h, w, L.stream_ptr()), "glorie_projmap")
+    return [coords, valid]
 
 
 def iproj(poses, disps, intrinsics):

@@ -627,6 +627,60 @@ class FusedUpdate:
 # --------------------------------------------------------------------------------------
 # correlation blocks
 # --------------------------------------------------------------------------------------
+class CorrSampler(torch.autograd.Function):
+    """corr_index_forward with its adjoint (corr.py:7-22): gradient for the volume, none for the coordinates"""
+
+    @staticmethod
+    def forward(ctx, volume, coords, radius):
+        ctx.save_for_backward(volume, coords)
+        ctx.radius = radius
+        corr, = droid_backends.corr_index_forward(volume, coords, radius)
+        return corr
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        volume, coords = ctx.saved_tensors
+        grad_output = grad_output.contiguous()
+        grad_volume, = droid_backends.corr_index_backward(volume, coords, grad_output, ctx.radius)
+        return grad_volume, None, None
+
+
+class CorrLayer(torch.autograd.Function):
+    """altcorr_forward with its adjoint (corr.py:79-94): gradients for both feature maps, zeros for the coordinates"""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, coords, r):
+        ctx.r = r
+        ctx.save_for_backward(fmap1, fmap2, coords)
+        corr, = droid_backends.altcorr_forward(fmap1, fmap2, coords, ctx.r)
+        return corr
+
+    @staticmethod
+    def backward(ctx, grad_corr):
+        fmap1, fmap2, coords = ctx.saved_tensors
+        grad_corr = grad_corr.contiguous()
+        fmap1_grad, fmap2_grad, coords_grad = droid_backends.altcorr_backward(fmap1, fmap2, coords, grad_corr, ctx.r)
+        return fmap1_grad, fmap2_grad, coords_grad, None
+
+
+class _PyramidLookup(torch.autograd.Function):
+    """The fused lookup of CorrBlock.__call__ under autograd: forward IS the corr_lookup_pyramid call of the no-grad path
+    (bit-identical values), backward the one-launch adjoint of all levels.  apply(coords, radius, *levels)."""
+
+    @staticmethod
+    def forward(ctx, coords, radius, *pyramid):
+        ctx.save_for_backward(coords)
+        ctx.radius = radius
+        ctx.shapes = [tuple(v.shape) for v in pyramid]
+        return droid_backends.corr_lookup_pyramid(list(pyramid), coords, radius)
+
+    @staticmethod
+    def backward(ctx, grad):
+        coords, = ctx.saved_tensors
+        grads = droid_backends.corr_lookup_pyramid_backward(ctx.shapes, coords, grad.contiguous(), ctx.radius)
+        return (None, None) + tuple(grads)
+
+
 class CorrBlock:
     """All-pairs correlation pyramid + windowed lookup (corr.py:25-76).
 
@@ -636,7 +690,11 @@ class CorrBlock:
     tiled (default on CUDA for radius 3): every plane is re-stored once, at construction, as 64-byte
     blocks of 4 rows x 8 columns (droid_backends.tile_corr_level) and looked up by the tiled kernel:
     same values bit for bit, 35 % less HBM traffic per lookup.  `corr_pyramid` then holds
-    [N*h1*w1, plane_l] tensors instead of the reference's [N, h1, w1, h2>>l, w2>>l]."""
+    [N*h1*w1, plane_l] tensors instead of the reference's [N, h1, w1, h2>>l, w2>>l].
+
+    Gradients: with gradients enabled and feature maps that require them the block is differentiable w.r.t. both maps
+    (matmul and avg_pool2d through torch, the lookup through _PyramidLookup).  The tiled re-store is a custom kernel that
+    cuts the graph, so tiled=None then resolves to the row-major pyramid and an explicit tiled=True raises."""
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=3, tiled=None):
         self.num_levels = num_levels
@@ -644,8 +702,12 @@ class CorrBlock:
         corr = CorrBlock.corr(fmap1, fmap2)
         batch, num, h1, w1, h2, w2 = corr.shape
         self.dims = (h1, w1, h2, w2)
+        needs_grad = torch.is_grad_enabled() and corr.requires_grad
+        if tiled and needs_grad:
+            raise RuntimeError("CorrBlock: tiled=True stores the pyramid with a kernel that has no gradient; use tiled=None "
+                               "or tiled=False with feature maps that require grad (or build the block under no_grad)")
         if tiled is None:
-            tiled = corr.is_cuda and radius == 3 and (h1 * w1) % 8 == 0 and corr.dtype == torch.float16
+            tiled = corr.is_cuda and radius == 3 and (h1 * w1) % 8 == 0 and corr.dtype == torch.float16 and not needs_grad
         self.tiled = bool(tiled)
         corr = corr.reshape(batch * num * h1 * w1, 1, h2, w2)
         self.corr_pyramid = []
@@ -674,7 +736,10 @@ class CorrBlock:
             out = droid_backends.corr_lookup_pyramid_tiled(self.corr_pyramid, c, self.dims[2], self.dims[3])
         else:
             pyr = [v if v.is_contiguous() else v.contiguous() for v in self.corr_pyramid]
-            out = droid_backends.corr_lookup_pyramid(pyr, c, self.radius)
+            if torch.is_grad_enabled() and any(v.requires_grad for v in pyr):
+                out = _PyramidLookup.apply(c, self.radius, *pyr)     # coordinates get no gradient (corr.py:22)
+            else:
+                out = droid_backends.corr_lookup_pyramid(pyr, c, self.radius)
         return out.view(batch, num, -1, ht, wd)
 
     @staticmethod
@@ -719,7 +784,10 @@ class CorrArena:
     layout "dm" (default for 4 levels): displacement-major, source-tiled lines (csrc/corr_dm.hip) - neighbouring source
     pixels share the 128-byte lines their windows read, and corr_encoder[0] can run inside the lookup launch
     (`lookup_encode`).  layout "tiled": per-pixel planes in 4x8 blocks (csrc/corr.hip, rounds 1-2; what other pyramid shapes
-    fall back to, and what the layout-agreement tests pass explicitly)."""
+    fall back to, and what the layout-agreement tests pass explicitly).
+
+    Inference only: building a slot and both lookups (`lookup_encode` included) are custom kernels without an adjoint, so
+    no gradient reaches the feature maps through an arena.  Use CorrBlock or AltCorrBlock with gradients."""
 
     def __init__(self, h, w, device, num_levels=4, radius=3, capacity=16, layout=None):
         assert radius == 3
@@ -872,7 +940,8 @@ class ArenaLookup:
 
 
 class AltCorrBlock:
-    """Volume-free correlation for long graphs (corr.py:79-145)."""
+    """Volume-free correlation for long graphs (corr.py:79-145).  With gradients enabled and feature maps that require them
+    the lookup goes through CorrLayer (gradients for the maps of both frames); otherwise it is the plain forward call."""
 
     def __init__(self, fmaps, num_levels=4, radius=3):
         self.num_levels = num_levels
@@ -882,7 +951,8 @@ class AltCorrBlock:
         self.pyramid = []
         for i in range(num_levels):
             self.pyramid.append(f.permute(0, 2, 3, 1).contiguous().view(B, N, H // 2 ** i, W // 2 ** i, C))
-            f = F.avg_pool2d(f, kernel_size=2, stride=2)
+            if i + 1 < num_levels:                 # maps whose last level is 1 x 1 (8 x 12 at 4 levels) have nothing left to pool
+                f = F.avg_pool2d(f, kernel_size=2, stride=2)
 
     def corr_fn(self, coords, ii, jj):
         B, N, H, W, S, _ = coords.shape
@@ -894,7 +964,10 @@ class AltCorrBlock:
             c = (coords / 2 ** i).reshape(B * N, S, H, W, 2).contiguous()
             f1 = f1.reshape((B * N,) + f1.shape[2:]).float().contiguous()
             f2 = f2.reshape((B * N,) + f2.shape[2:]).float().contiguous()
-            corr, = droid_backends.altcorr_forward(f1, f2, c.float(), self.radius)
+            if torch.is_grad_enabled() and (f1.requires_grad or f2.requires_grad):
+                corr = CorrLayer.apply(f1, f2, c.float(), self.radius)    # a zero gradient for the coordinates (corr.py:94)
+            else:
+                corr, = droid_backends.altcorr_forward(f1, f2, c.float(), self.radius)
             outs.append(corr.view(B, N, S, -1, H, W).permute(0, 1, 3, 4, 5, 2))
         return torch.cat(outs, dim=2)
 
@@ -925,7 +998,10 @@ class OtfCorrBlock:
     """Volume-free correlation on the matrix cores (csrc/corr_otf.hip): same call contract as
     AltCorrBlock (`OtfCorrBlock(fmaps)(coords, ii, jj)` -> [B, N, 196, H, W]) and the values a
     CorrBlock volume lookup returns up to fp16 rounding, without the 61 MB/edge volume.
-    fmaps: [1, F, C, H, W] (video.fmaps viewed like factor_graph.py:266-268)."""
+    fmaps: [1, F, C, H, W] (video.fmaps viewed like factor_graph.py:266-268).
+
+    Inference only: neither the lookup nor `lookup_encode` (the lookup with corr_encoder[0] fused behind it) has an adjoint;
+    AltCorrBlock is the volume-free block that differentiates."""
 
     def __init__(self, fmaps, num_levels=4, radius=3):
         assert radius == 3

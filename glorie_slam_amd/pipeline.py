@@ -795,12 +795,23 @@ class SequenceRunner:
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         cap.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(cap):
-            graph.capture_begin(pool=self._map_pool)
-            try:
-                loss = iteration()
-            finally:
-                graph.capture_end()
+        # no automatic garbage collection while the capture is open: the iteration runs its backward on the autograd thread, and a
+        # collection that starts there finalises whatever cyclic garbage earlier work left behind (graphs, events, contexts) -
+        # device calls from another thread inside a global-mode capture, which end the process.  Nothing is collected here
+        # either (FactorGraph._capture says why); the collector is only held off for the few milliseconds of the recording.
+        import gc
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.stream(cap):
+                graph.capture_begin(pool=self._map_pool)
+                try:
+                    loss = iteration()
+                finally:
+                    graph.capture_end()
+        finally:
+            if gc_was_on:
+                gc.enable()
         torch.cuda.current_stream(dev).wait_stream(cap)
         return graph, loss
 

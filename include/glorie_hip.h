@@ -183,6 +183,37 @@ int glorie_altcorr_fwd(const float* fmap1, const float* fmap2, const float* coor
                        float* out, int B, int S, int H, int W, int H2, int W2, int C,
                        int radius, void* stream);
 
+/* droid_backends.corr_index_backward(volume, coords, corr_grad, radius)
+ *   reference: src/lib/droid.cpp:182-193, src/lib/correlation_kernels.cu:73-124,157-185
+ * The exact adjoint of glorie_corr_index_fwd: coords [N,2,h1,w1] f32 (scaled to this level), corr_grad
+ * [N,2r+1,2r+1,h1,w1] and volume_grad [N,h1,w1,h2,w2] of `dtype` (f16|f32).  volume_grad is FULLY overwritten, zeros
+ * included, by one pass of wide stores (source pixel (n,y,x) owns its plane: no memset, no atomics, bitwise repeatable;
+ * the reference zero-fills and accumulates).  Weights, products and the <= 4-term sum are fp32 for both dtypes and an f16
+ * result is rounded once at the store; the reference rounds every step in half, so f16 results are NOT claimed
+ * bit-identical to its half sequence.  Element offsets are 64-bit.  Coordinates must be finite (huge ones are fine).
+ * radius <= 7. */
+int glorie_corr_index_bwd(const float* coords, const void* corr_grad, void* volume_grad,
+                          int N, int h1, int w1, int h2, int w2, int radius, int dtype, void* stream);
+
+/* Adjoint of glorie_corr_lookup_pyramid (src/modules/droid_net/corr.py:43-53 under autograd: four CorrSampler.backward
+ * calls): coords [N,2,h1,w1] f32 UNscaled (level l uses coords / 2^l), grad [N, L*(2r+1)^2, h1, w1], volume_grads[l]
+ * [N,h1,w1,h2>>l,w2>>l].  One launch for all levels; ownership, full overwrite and the f16 rule as above. */
+int glorie_corr_lookup_pyramid_bwd(const float* coords, const void* grad, void* const* volume_grads, int num_levels,
+                                   int N, int h1, int w1, int h2, int w2, int radius, int dtype, void* stream);
+
+/* droid_backends.altcorr_backward(fmap1, fmap2, coords, corr_grad, radius)
+ *   reference: src/lib/droid.cpp:207-219, src/lib/altcorr_kernel.cu:153-286,321-356
+ * The adjoint of glorie_altcorr_fwd (f32 only): corr_grad [B,S,(2r+1)^2,H,W], channel (iy-1) + (2r+1)(ix-1).
+ * fmap1_grad [B,H,W,C] is written (each row owned by its source pixel: plain stores, bitwise repeatable).
+ * fmap2_grad [B,H2,W2,C] is ADDED to with float atomics: the caller zero-fills it.  4 x 4 source tiles pre-sum their
+ * contributions per target pixel over the box of their windows (an LDS table of tap gradients times the tile's feature
+ * rows) and add one row per touched target; a tile whose box holds more than 400 targets (scattered coordinates) adds one
+ * row per tap.  The order of float atomic adds is free: fmap2_grad is
+ * not bitwise repeatable on general data.  Coordinates get no gradient.  radius <= 7. */
+int glorie_altcorr_bwd(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad,
+                       float* fmap1_grad, float* fmap2_grad, int B, int S, int H, int W, int H2, int W2, int C,
+                       int radius, void* stream);
+
 /* Bookkeeping of FactorGraph.update between the update operator and the BA, in one launch
  *   reference: src/factor_graph.py:219-223 (target = coords1 + delta, damping[unique(ii)] = damping), :248
  *   (BA damping 0.2 * damping + EP), :256 (age += 1)
@@ -387,6 +418,15 @@ int glorie_reproject(const float* poses, const float* disps, const float* intrin
 int glorie_frame_distance(const float* poses, const float* disps, const float* intrinsics,
                           const int64_t* ii, const int64_t* jj, float* dist,
                           int K, int h, int w, float beta, void* stream);
+
+/* droid_backends.projmap(poses, disps, intrinsics, ii, jj)
+ *   reference: src/lib/droid.cpp:141-156, src/lib/droid_kernels.cu:427-516,1466-1491
+ * poses [B,7], disps [B,h,w], intrinsics [4] (one camera), ii/jj [N] int64.  coords [N,h,w,2]: the pixel grid itself
+ * where Z <= 0.01, the projection into frame jj otherwise; valid [N,h,w,1] = Z > 0.25.  Not glorie_reproject (thresholds
+ * 0.1 / 0.2, no grid fallback, per-frame intrinsics). */
+int glorie_projmap(const float* poses, const float* disps, const float* intrinsics,
+                   const int64_t* ii, const int64_t* jj, float* coords, float* valid,
+                   int N, int h, int w, void* stream);
 
 /* droid_backends.iproj(poses, disps, intrinsics)
  *   reference: src/lib/droid.cpp:161-169, src/lib/droid_kernels.cu:779-850,1521-1544
