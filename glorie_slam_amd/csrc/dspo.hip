@@ -252,11 +252,25 @@ __global__ __launch_bounds__(kBaThreads) void dspo2_update_kernel(BaWork wk, Dsp
   const int px = blockIdx.x * kBaThreads + tid;
   if (px >= HW) return;
   const PriorJ J = prior_jacobians(a.mono[(size_t)k * HW + px], a.vmask[(size_t)k * HW + px] != 0, a.alpha);
-  const float dz = wk.Q[(size_t)s * HW + px] *
-                   (wk.W[(size_t)s * HW + px] - (J.Js * J.Jd * ds + J.Jq * J.Jd * dq));
+  const float Qp = wk.Q[(size_t)s * HW + px];
+  const float rhs = wk.W[(size_t)s * HW + px] - (J.Js * J.Jd * ds + J.Jq * J.Jd * dq);
   // disp_retr then clamp(min=0) (ba.py:210-214)
-  a.disps[(size_t)k * HW + px] = fmaxf(a.disps[(size_t)k * HW + px] + dz, 0.0f);
-  if (dz_out) dz_out[(size_t)s * HW + px] = dz;
+  if (!dz_out) {
+    // the product path: dz = Qp rhs and its addition are one fma (one rounding), written out so that it stays one
+    a.disps[(size_t)k * HW + px] = fmaxf(__builtin_fmaf(Qp, rhs, a.disps[(size_t)k * HW + px]), 0.0f);
+    return;
+  }
+  // A caller that asks for the step gets the step that was applied: dz is rounded once, stored, and that value is added,
+  // as the reference's `disps + dz` does.  Through the fma above the stored disparity comes from the unrounded product,
+  // and fmaxf(d + dz_out, 0) missed it by an ulp wherever one rounding and two differ.
+  const float dz = Qp * rhs;
+  float dnew;
+  {
+#pragma clang fp contract(off)
+    dnew = a.disps[(size_t)k * HW + px] + dz;
+  }
+  a.disps[(size_t)k * HW + px] = fmaxf(dnew, 0.0f);
+  dz_out[(size_t)s * HW + px] = dz;
 }
 
 }  // namespace glorie
