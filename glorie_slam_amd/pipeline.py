@@ -12,6 +12,7 @@ list being rebuilt under the renderer, the training path feeding FeatureAdam wit
 keeps up with the tracker (every kept keyframe is mapped before the next frame is tracked).
 """
 import time
+import types
 
 import torch
 
@@ -251,7 +252,7 @@ class SequenceRunner:
         if radius_map is not None:
             radius = radius_map[jj, ii]
         elif self.npc.use_dynamic_radius:
-            radius = torch.full_like(d, 0.5 * (self.npc.radius_add + self.npc.radius_query))
+            radius = torch.full_like(d, self._const_radius())
         return ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous(), d, col, ii, jj, radius
 
     def map_keyframe(self, k):
@@ -264,7 +265,7 @@ class SequenceRunner:
         trains on its render depth (proxy or aligned mono), and a frame with too few tracker depths is skipped.  With
         mapping_schedule the iterations follow the reference's schedule instead (_optimize_scheduled).  With mapping_vis
         the keyframe's contact sheet is written after its last iteration (_visualize)"""
-        npc, dec, ren = self.npc, self.decoders, self.renderer
+        npc = self.npc
         self._render_views = None
         self._vis_depths = None
         try:
@@ -292,10 +293,8 @@ class SequenceRunner:
                     added.append(self._anchor_grad_points(k, rmaps, view=ins_view))
             if npc.pts_num() == 0:
                 return None
-            if self.mapping_schedule:
-                # frame_pts_add (mapper.py:305-324): one host read per keyframe
-                return self._optimize_scheduled(k, rmaps, sum(int(a) for a in added))
-            return self._optimize_keyframe(k, rmaps)
+            # frame_pts_add (mapper.py:305-324): one host read per keyframe on the schedule
+            return self._optimize_keyframe(k, rmaps, sum(int(a) for a in added) if self.mapping_schedule else None)
         finally:
             self._render_views = None
             self._read_deform_stats()
@@ -331,128 +330,183 @@ class SequenceRunner:
             warp["value"].copy_(w.detach())
         return loss / seen.sum().clamp_min(1), depth, colour, seen
 
-    def _optimize_keyframe(self, k, rmaps):
-        """the mapping iterations of map_keyframe (after the insertion)"""
-        npc, dec, ren = self.npc, self.decoders, self.renderer
-        geo = npc.geo_feats.detach().clone().requires_grad_(True)
-        col_f = npc.col_feats.detach().clone().requires_grad_(True)
-        dec.train()
-        for p in dec.parameters():
-            p.requires_grad_(True)
+    def _map_setup(self, k, rmaps=None, final=None, table=False):
+        """what the iterations of keyframe k - or, with final = (window, views, per, pix_warping) and k None, of one pass
+        of final_refine - hold fixed, as a namespace: geo, col_f (the clones of the two feature tables that are trained);
+        view (of k), window, views, per, and `win`, the dict of the last three with frame_ids and ray_frame (None for k
+        alone); warp (win plus the window's c2ws and the device table of its images, with pix_warping); rq (frame -> its
+        query radius map, with colour-gradient radii) and const_r (the constant radius otherwise); with `table` the
+        WindowTable of the window (also win["table"]); frustum and row_masks (keyframes with frustum selection)"""
+        npc, ren = self.npc, self.renderer
+        s = types.SimpleNamespace(geo=npc.geo_feats.detach().clone().requires_grad_(True),
+                                  col_f=npc.col_feats.detach().clone().requires_grad_(True), view=None, win=None,
+                                  warp=None, rq=None, table=None, frustum=None, row_masks=None)
         with torch.no_grad():
-            view = self._keyframe_view(k)
-            win = self._map_window(k, view) if (self.pix_warping or self.keyframe_selection_method) else None
-            warp = win if self.pix_warping else None
-            self.windows.append(win["window"] if win is not None else [k])
-            # the rows the iterations may change: inside the frustum of this view, against the depth the iteration reads
-            # (get_mask_from_c2w, mapper.py:591-595); the count stays on the device until the keyframe is done
-            frustum = frustum_feature_mask(npc.cloud_pos(), view[1], view[0], ren.fx, ren.fy, ren.cx, ren.cy,
-                                           self.video.ht, self.video.wd, self.frustum_edge) \
-                if self.frustum_feature_selection else None
-            row_masks = {id(geo): frustum[0], id(col_f): frustum[0]} if frustum is not None else None
-            # every window frame's own query radius map, built once per keyframe; the iteration gathers from them
-            rq = None
-            if rmaps is not None:
-                rq = {f: (rmaps[1] if f == k else self._radius_maps(f, win["views"][f], add=False)[1])
-                      for f in (win["window"] if win is not None else [k])}
-            if win is None:
-                # every iteration's pixel draw in one transfer ([iteration][ii | jj][ray], the generator's order per iteration)
-                draws = torch.stack([torch.stack([torch.randint(0, self.video.wd, (self.map_rays,), generator=self.gen),
-                                                  torch.randint(0, self.video.ht, (self.map_rays,), generator=self.gen)])
-                                     for _ in range(self.map_iters)]).to(self.device) if self.map_iters else None
-                # one look at the keyframe's depth map (a host round trip per KEYFRAME): if every pixel carries a depth, no
-                # iteration needs the host - the renderer skips its per-batch zero-depth check and the iteration can be
-                # recorded
-                all_depth = bool((view[0] > 0).all())
+            if final is None:
+                s.view = self._keyframe_view(k)
+                windowed, pix_warping = bool(self.pix_warping or self.keyframe_selection_method), self.pix_warping
+                window = self._map_window(k, s.view) if windowed else [k]
+                s.per = self.map_rays // len(window)      # (frames skipped below still count, mapper.py:584)
+                s.window, s.views = self._window_views(window, {k: s.view})
+                if self.frustum_feature_selection:
+                    # the rows the iterations may change: inside the frustum of this view, against the depth the iteration
+                    # reads (get_mask_from_c2w, mapper.py:591-595); the count stays on the device until the keyframe is done
+                    s.frustum = frustum_feature_mask(npc.cloud_pos(), s.view[1], s.view[0], ren.fx, ren.fy, ren.cx, ren.cy,
+                                                     self.video.ht, self.video.wd, self.frustum_edge)
+                    s.row_masks = {id(s.geo): s.frustum[0], id(s.col_f): s.frustum[0]}
             else:
-                # map_rays // len(window) pixels of every window frame per iteration (pixs_per_image, mapper.py:584), all
-                # iterations drawn up front: [iteration][ii | jj][frame-major rays]
-                per, n_win = win["per"], len(win["window"])
-                draws = torch.stack([torch.stack([torch.cat(c) for c in zip(*[
-                    (torch.randint(0, self.video.wd, (per,), generator=self.gen),
-                     torch.randint(0, self.video.ht, (per,), generator=self.gen)) for _ in range(n_win)])])
-                    for _ in range(self.map_iters)]).to(self.device) if self.map_iters else None
-                all_depth = bool(torch.stack([(win["views"][f][0] > 0).all() for f in win["window"]]).all())
-        use_graph = bool(getattr(self, "map_graph", True)) and all_depth and self.map_iters >= 4 and \
-            str(self.device).startswith("cuda") and getattr(ren, "use_train_path", True)
-        opt = FeatureAdam([{"params": list(dec.parameters()), "lr": 0.005}, {"params": [geo], "lr": 0.005},
-                           {"params": [col_f], "lr": 0.005}], capturable=use_graph)
-        self.last_optimizer = opt                            # (tests: step bookkeeping)
-        pix = draws[0].clone() if self.map_iters else None   # the iteration reads its pixels from this buffer
+                (s.window, s.views, s.per, pix_warping), windowed = final, True
+            window, views = s.window, s.views
+            # every window frame's own query radius map, built once per keyframe; the iteration gathers from them
+            if self.color_grad is not None:
+                s.rq = {f: (rmaps[1] if rmaps is not None and f == k else self._radius_maps(f, views[f], add=False)[1])
+                        for f in window}
+            s.const_r = None if s.rq is not None else self._const_radius()
+            if pix_warping or table:
+                c2ws = torch.stack([views[f][1] for f in window]).float().contiguous()
+            if table:
+                s.table = WindowTable([views[f][0] for f in window], [self.images[f] for f in window], c2ws,
+                                      [s.rq[f] for f in window] if s.rq else None, channels_first=True)
+            if windowed:
+                frame_ids = torch.tensor(window, dtype=torch.int64).to(self.device)
+                s.win = {"window": window, "views": views, "per": s.per, "frame_ids": frame_ids,
+                         "ray_frame": frame_ids.repeat_interleave(s.per)}
+                if table:
+                    s.win["table"] = s.table
+                if pix_warping:
+                    s.warp = dict(s.win, c2ws=c2ws, table=FrameTable([self.images[f] for f in window], channels_first=True),
+                                  value=torch.zeros((), device=self.device), first=None)
+        return s
 
-        def iteration():
+    def _all_depth(self, s):
+        """one look at the window's depth maps (a host round trip per KEYFRAME): if every pixel carries a depth, no
+        iteration needs the host - the renderer skips its per-batch zero-depth check and the iteration can be recorded"""
+        return bool(torch.stack([(s.views[f][0] > 0).all() for f in s.window]).all())
+
+    def _train(self, s, n_it, opt, rays, all_depth, probe_k, before=None, record=False, probe_extra=None):
+        """`n_it` mapping iterations on the setup `s` (_map_setup) with the optimizer `opt`, then the trained tables go
+        back into the cloud.  An iteration is before(it) (the caller's switches), rays(it) under no_grad -> ((ro, rd, d,
+        gt_col, radius), keywords of _mapping_loss, further entries of the probe's dict), zero_grad, the loss, map_probe
+        under the id `probe_k`, backward, step.  record: iteration 1 is recorded into a hipGraph and replayed for itself and
+        every later one (rays must not read `it` then).  -> (seconds between the two synchronisations, (first, last) loss,
+        NaN for no iteration); the pixel-warping term's pair is left in s.warp["first"] / ["value"]"""
+        npc, ren, warp = self.npc, self.renderer, s.warp
+        frustum = s.frustum[0] if s.frustum is not None else None
+        self.last_optimizer = opt                            # (tests: step bookkeeping)
+
+        def iteration(it):
             with torch.no_grad():
-                if win is None:
-                    ro, rd, d, gt_col, _, _, radius = self._keyframe_rays(k, view=view, pix=(pix[0], pix[1]),
-                                                                          radius_map=rq[k] if rq else None)
-                else:
-                    ro, rd, d, gt_col, radius = self._window_rays(win, pix, rq)
+                (ro, rd, d, gt_col, radius), loss_kw, extra = rays(it)
             opt.zero_grad()
-            loss, depth, colour, seen = self._mapping_loss(ro, rd, d, gt_col, radius, geo, col_f, warp)
+            # the colour decoder is not run in the geometry stage: no gradient is formed for its table there
+            col_f = s.col_f.detach() if loss_kw.get("stage") == "geometry" else s.col_f
+            loss, depth, colour, seen = self._mapping_loss(ro, rd, d, gt_col, radius, s.geo, col_f, warp, **loss_kw)
             if self.map_probe is not None and not torch.cuda.is_current_stream_capturing():
-                self.map_probe(k, dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(), colour=colour.detach(),
-                                       seen=seen, loss=loss.detach(), warp=warp, window=win,
-                                       frustum=frustum[0] if frustum is not None else None, radius=radius,
-                                       pix=pix))
+                self.map_probe(probe_k, dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(),
+                                             colour=colour.detach(), seen=seen, loss=loss.detach(), warp=warp, window=s.win,
+                                             frustum=frustum, radius=radius, **extra, **(probe_extra or {})))
             loss.backward()
-            opt.step(row_masks=row_masks)
+            opt.step(row_masks=s.row_masks)
             return loss.detach()
 
-        first = last = None
+        first = last = graph = None
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         ren.assume_depth = all_depth
         try:
-            graph = None
-            for it in range(self.map_iters):
-                if it:
-                    pix.copy_(draws[it])
-                if graph is not None:
-                    graph.replay()
-                    continue
-                if use_graph and it == 1:
+            for it in range(n_it):
+                if before is not None:
+                    before(it)
+                if record and it == 1:
                     # Iteration 0 ran eagerly (it sizes the scratch arenas, creates the Adam moments and sends the pointer
                     # table); iteration 1 is RECORDED - forward, masked loss, backward (incl. its second stream for the weight
                     # gradients), Adam with the step count in device memory - and replayed for itself and every later one
                     # (mapper.py:586-624 runs 150-1500 of them per keyframe on the same tensors).
                     try:
-                        graph, last = self._capture_iteration(iteration)
+                        graph, last = self._capture_iteration(lambda: iteration(it))
                     except Exception as exc:      # a failed recording must not take the mapper down
                         import warnings
                         warnings.warn(f"hipGraph capture of the mapping iteration failed ({exc!r}); running eagerly")
-                        graph, use_graph = None, False
+                        record = False
                         opt.capturable_fallback()
-                    if graph is not None:
-                        graph.replay()
-                        continue
-                last = iteration()
+                if graph is not None:
+                    graph.replay()
+                    continue
+                last = iteration(it)
                 if first is None:
                     first = last.clone()
                     if warp is not None:
                         warp["first"] = warp["value"].clone()
             if graph is not None:
                 # host bookkeeping: the eager iteration and the recording itself each counted one step, the device did
-                # 1 + (map_iters - 1)
-                opt.advance(self.map_iters - 2)
+                # 1 + (n_it - 1)
+                opt.advance(n_it - 2)
                 last = last.clone()
                 self.map_graph_stats["captures"] += 1
-                self.map_graph_stats["replays"] += self.map_iters - 1
+                self.map_graph_stats["replays"] += n_it - 1
         finally:
             ren.assume_depth = False
         torch.cuda.synchronize()
-        self.timing["map_iter_ms"].append(1e3 * (time.perf_counter() - t0) / max(self.map_iters, 1))
+        elapsed = time.perf_counter() - t0
         with torch.no_grad():
-            npc.update_geo_feats(geo.detach())
-            npc.update_col_feats(col_f.detach())
-        dec.eval()
-        self.losses.append((float(first), float(last)))
-        if warp is not None:
-            self.warp_losses.append((float(warp["first"]), float(warp["value"])))
-        if frustum is not None:
-            self.frustum_counts.append(int(frustum[1]))
+            npc.update_geo_feats(s.geo.detach())
+            npc.update_col_feats(s.col_f.detach())
+        return elapsed, (float(first), float(last)) if n_it else (float("nan"), float("nan"))
+
+    def _optimize_keyframe(self, k, rmaps, frame_pts_add=None):
+        """the mapping iterations of map_keyframe (after the insertion) and their bookkeeping: the one-stage loop
+        (_optimize_default) or, with mapping_schedule, the reference's schedule for `frame_pts_add` inserted points
+        (_optimize_scheduled)"""
+        s = self._map_setup(k, rmaps, table=self.mapping_schedule)
+        self.decoders.train()
+        if self.mapping_schedule:
+            n_it, elapsed, losses = self._optimize_scheduled(k, s, frame_pts_add)
+        else:
+            n_it, elapsed, losses = self._optimize_default(k, s)
+        self.decoders.eval()
+        self.timing["map_iter_ms"].append(1e3 * elapsed / max(n_it, 1))
+        self.losses.append(losses)
+        self.windows.append(s.window)
+        if s.warp is not None and n_it:
+            self.warp_losses.append((float(s.warp["first"]), float(s.warp["value"])))
+        if s.frustum is not None:
+            self.frustum_counts.append(int(s.frustum[1]))
         if self.mapping_vis is not None:
-            self._visualize(k, view, rq[k] if rq else None, self.map_iters)
-        return self.losses[-1]
+            self._visualize(k, s.view, s.rq[k] if s.rq else None, n_it)
+        return losses
+
+    def _optimize_default(self, k, s):
+        """map_iters iterations in the colour stage on uniform pixel draws, every decoder trained at 0.005; recorded into a
+        hipGraph when map_graph is set and every window pixel carries a depth -> (iterations, seconds, (first, last))"""
+        dec, n_it, W, H = self.decoders, self.map_iters, self.video.wd, self.video.ht
+        for p in dec.parameters():
+            p.requires_grad_(True)
+        # map_rays // len(window) pixels of every window frame per iteration (pixs_per_image, mapper.py:584), all
+        # iterations drawn up front in one transfer: [iteration][ii | jj][frame-major rays], in the generator's order per
+        # iteration and frame
+        draws = torch.stack([torch.stack([torch.cat(c) for c in zip(*[
+            (torch.randint(0, W, (s.per,), generator=self.gen), torch.randint(0, H, (s.per,), generator=self.gen))
+            for _ in s.window])]) for _ in range(n_it)]).to(self.device) if n_it else None
+        all_depth = self._all_depth(s)
+        record = bool(getattr(self, "map_graph", True)) and all_depth and n_it >= 4 and \
+            str(self.device).startswith("cuda") and getattr(self.renderer, "use_train_path", True)
+        opt = FeatureAdam([{"params": list(dec.parameters()), "lr": 0.005}, {"params": [s.geo], "lr": 0.005},
+                           {"params": [s.col_f], "lr": 0.005}], capturable=record)
+        pix = draws[0].clone() if n_it else None             # the iteration reads its pixels from this buffer
+
+        def before(it):
+            if it:
+                pix.copy_(draws[it])
+
+        def rays(it):
+            if s.win is None:
+                ro, rd, d, gt_col, _, _, radius = self._keyframe_rays(k, view=s.view, pix=(pix[0], pix[1]),
+                                                                      radius_map=s.rq[k] if s.rq else None)
+            else:
+                ro, rd, d, gt_col, radius = self._window_rays(s.win, pix, s.rq)
+            return (ro, rd, d, gt_col, radius), {}, dict(pix=pix)
+
+        return (n_it,) + self._train(s, n_it, opt, rays, all_depth, k, before=before, record=record)
 
     # ---- the reference's schedule (mapper.py:390-515, :598-638), mapping_schedule=True ------------------------------
     def _const_radius(self):
@@ -479,103 +533,52 @@ class SequenceRunner:
             bound = int(n * sc["geo_iter_ratio"])
         return n, min(n, bound + 1)
 
-    def _optimize_scheduled(self, k, rmaps, frame_pts_add):
+    def _optimize_scheduled(self, k, s, frame_pts_add):
         """the mapping iterations of map_keyframe on the reference's schedule.  One WindowTable and ValidIndex per
         keyframe over its window; every iteration is one sampling launch and one gate launch in front of the loss, its
-        stage and learning rates by schedule_of.  Runs eagerly"""
-        npc, dec, ren, sc = self.npc, self.decoders, self.renderer, self.schedule
+        stage and learning rates by schedule_of.  Runs eagerly -> (iterations, seconds, (first, last))"""
+        dec, ren, sc = self.decoders, self.renderer, self.schedule
         init = not self.schedules
         n_it, n_geo = self.schedule_of(init, frame_pts_add)
         rates = sc["rates"]["init" if init else "stage"]
-        geo = npc.geo_feats.detach().clone().requires_grad_(True)
-        col_f = npc.col_feats.detach().clone().requires_grad_(True)
         geo_params, col_params = list(dec.geo_decoder.parameters()), list(dec.color_decoder.parameters())
         flags = [(p, p.requires_grad) for p in dec.parameters()]
-        with torch.no_grad():
-            view = self._keyframe_view(k)
-            win = self._map_window(k, view) if (self.pix_warping or self.keyframe_selection_method) else None
-            warp = win if self.pix_warping else None
-            window = win["window"] if win is not None else [k]
-            views = win["views"] if win is not None else {k: view}
-            per = win["per"] if win is not None else self.map_rays
-            self.windows.append(window)
-            frustum = frustum_feature_mask(npc.cloud_pos(), view[1], view[0], ren.fx, ren.fy, ren.cx, ren.cy,
-                                           self.video.ht, self.video.wd, self.frustum_edge) \
-                if self.frustum_feature_selection else None
-            row_masks = {id(geo): frustum[0], id(col_f): frustum[0]} if frustum is not None else None
-            rq = None
-            if rmaps is not None:
-                rq = [rmaps[1] if f == k else self._radius_maps(f, views[f], add=False)[1] for f in window]
-            table = WindowTable([views[f][0] for f in window], [self.images[f] for f in window],
-                                torch.stack([views[f][1] for f in window]).float(), rq, channels_first=True)
-            index = ValidIndex(table, "all" if self.render_depth == "mono" else "depth")
-            const_r = None if rq is not None else self._const_radius()
-            # every iteration's draws in one transfer
-            draws = torch.randint(0, DRAW_RANGE, (n_it, len(window) * per), generator=self.gen).to(self.device)
-            # one look per keyframe: when every drawn ray is sure to carry a depth the renderer needs no host check
-            all_depth = bool((index.counts > 0).all()) if index.mode == "depth" \
-                else bool(torch.stack([(d > 0).all() for d in table.depths]).all())
+        index = ValidIndex(s.table, "all" if self.render_depth == "mono" else "depth")
+        # every iteration's draws in one transfer
+        draws = torch.randint(0, DRAW_RANGE, (n_it, len(s.window) * s.per), generator=self.gen).to(self.device)
+        # one look per keyframe: when every drawn ray is sure to carry a depth the renderer needs no host check
+        all_depth = bool((index.counts > 0).all()) if index.mode == "depth" else self._all_depth(s)
         trained = ([] if sc["fix_geo_decoder"] else geo_params) + ([] if sc["fix_color_decoder"] else col_params)
-        opt = FeatureAdam([{"params": trained, "lr": 0.0}, {"params": [geo], "lr": 0.0}, {"params": [col_f], "lr": 0.0}])
-        self.last_optimizer = opt
-        first = last = None
-        dec.train()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        ren.assume_depth = all_depth
+        opt = FeatureAdam([{"params": trained, "lr": 0.0}, {"params": [s.geo], "lr": 0.0}, {"params": [s.col_f], "lr": 0.0}])
+        stage_of = lambda it: "geometry" if it < n_geo else "color"
+
+        def before(it):
+            if it in (0, n_geo):
+                # the colour decoder is not run in the geometry stage: no gradient is formed for it there
+                for p in col_params:
+                    p.requires_grad_(stage_of(it) == "color" and not sc["fix_color_decoder"])
+            for group, key in zip(opt.param_groups, ("decoders_lr", "geometry_lr", "color_lr")):
+                group["lr"] = float(rates[stage_of(it)][key])
+
+        def rays(it):
+            stage = stage_of(it)
+            ro, rd, d, gt_col, radius, ii, jj = sample_window_rays(s.table, index, draws[it], s.per, ren.fx, ren.fy, ren.cx,
+                                                                   ren.cy, const_radius=s.const_r)
+            gate, gate_stats = depth_gate(d)
+            extra = dict(pix=torch.stack([ii, jj]), stage=stage, gate=gate, gate_stats=gate_stats, ii=ii, jj=jj,
+                         lrs=dict(rates[stage])) if self.map_probe is not None else {}
+            return (ro, rd, d, gt_col, radius), dict(stage=stage, gate=gate, w_geo=sc["w_geo_loss"],
+                                                     w_color=sc["w_color_loss"]), extra
+
         try:
             for p in geo_params:
                 p.requires_grad_(not sc["fix_geo_decoder"])
-            for it in range(n_it):
-                stage = "geometry" if it < n_geo else "color"
-                if it in (0, n_geo):
-                    # the colour decoder is not run in the geometry stage: no gradient is formed for it there
-                    for p in col_params:
-                        p.requires_grad_(stage == "color" and not sc["fix_color_decoder"])
-                lrs = rates[stage]
-                for group, key in zip(opt.param_groups, ("decoders_lr", "geometry_lr", "color_lr")):
-                    group["lr"] = float(lrs[key])
-                with torch.no_grad():
-                    ro, rd, d, gt_col, radius, ii, jj = sample_window_rays(table, index, draws[it], per, ren.fx, ren.fy,
-                                                                           ren.cx, ren.cy, const_radius=const_r)
-                    gate, gate_stats = depth_gate(d)
-                opt.zero_grad()
-                loss, depth, colour, seen = self._mapping_loss(
-                    ro, rd, d, gt_col, radius, geo, col_f if stage == "color" else col_f.detach(), warp, stage=stage,
-                    gate=gate, w_geo=sc["w_geo_loss"], w_color=sc["w_color_loss"])
-                if self.map_probe is not None:
-                    self.map_probe(k, dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(), colour=colour.detach(),
-                                           seen=seen, loss=loss.detach(), warp=warp, window=win,
-                                           frustum=frustum[0] if frustum is not None else None, radius=radius,
-                                           pix=torch.stack([ii, jj]), stage=stage, gate=gate, gate_stats=gate_stats, ii=ii,
-                                           jj=jj, lrs=dict(lrs)))
-                loss.backward()
-                opt.step(row_masks=row_masks)
-                last = loss.detach()
-                if first is None:
-                    first = last
-                    if warp is not None:
-                        warp["first"] = warp["value"].clone()
+            elapsed, losses = self._train(s, n_it, opt, rays, all_depth, k, before=before)
         finally:
-            ren.assume_depth = False
             for p, req in flags:
                 p.requires_grad_(req)
-        torch.cuda.synchronize()
-        self.timing["map_iter_ms"].append(1e3 * (time.perf_counter() - t0) / max(n_it, 1))
-        with torch.no_grad():
-            npc.update_geo_feats(geo.detach())
-            npc.update_col_feats(col_f.detach())
-        dec.eval()
-        nan = float("nan")
-        self.losses.append((float(first), float(last)) if n_it else (nan, nan))
         self.schedules.append((n_it, n_geo))
-        if warp is not None and n_it:
-            self.warp_losses.append((float(warp["first"]), float(warp["value"])))
-        if frustum is not None:
-            self.frustum_counts.append(int(frustum[1]))
-        if self.mapping_vis is not None:
-            self._visualize(k, view, rq[-1] if rq else None, n_it)
-        return self.losses[-1]
+        return n_it, elapsed, losses
 
     # ---- the per-keyframe contact sheet (mapper.py:664-673) --------------------------------------------------------
     def _visualize(self, k, view, r_query, n_it):
@@ -602,7 +605,7 @@ class SequenceRunner:
             else:
                 mono, droid = self._mono_prior(k), render_depth
             if r_query is None and npc.use_dynamic_radius:
-                r_query = torch.full_like(render_depth, 0.5 * (npc.radius_add + npc.radius_query))
+                r_query = torch.full_like(render_depth, self._const_radius())
             cfg = self._mono_cfg()
             cfg["mapping"] = dict(cfg["mapping"], mapping_window_size=self.mapping_window_size)
             self.visualizer.vis(int(self.video.timestamp[k]), n_it - 1, None, render_depth, droid, mono,
@@ -717,29 +720,20 @@ class SequenceRunner:
                                           generator=self.gen)
 
     def _map_window(self, k, view):
-        """the mapping window of keyframe k (k last) with its views, rays per frame and frame ids; with pix_warping also
-        the window's c2ws and the device table of its images.  Without a keyframe_selection_method: k and the
+        """the mapping window of keyframe k (keyframe ids, k last).  Without a keyframe_selection_method: k and the
         mapping_window_size - 1 most recent earlier keyframes; with one: the selected keyframes, k-1, k"""
         if self.keyframe_selection_method:
-            window = self._select_keyframes(k, view) + ([k - 1] if k > 0 else []) + [k]
-        else:
-            window = list(range(max(0, k - self.mapping_window_size + 1), k + 1))
+            return self._select_keyframes(k, view) + ([k - 1] if k > 0 else []) + [k]
+        return list(range(max(0, k - self.mapping_window_size + 1), k + 1))
+
+    def _window_views(self, window, known=()):
+        """(the frames of `window` that are not skipped, frame -> (depth, c2w)): `known` views as given, the others their
+        render view with render_depth (None: skipped), else their keyframe view"""
+        fetch = self._render_view if self.render_depth is not None else self._keyframe_view
         with torch.no_grad():
-            per = self.map_rays // len(window)          # (frames skipped below still count, mapper.py:584)
-            if self.render_depth is not None:
-                views = {f: (view if f == k else self._render_view(f)) for f in window}
-                window = [f for f in window if views[f] is not None]
-                views = {f: views[f] for f in window}
-            else:
-                views = {f: (view if f == k else self._keyframe_view(f)) for f in window}
-            frame_ids = torch.tensor(window, dtype=torch.int64).to(self.device)
-            win = {"window": window, "views": views, "per": per, "frame_ids": frame_ids,
-                   "ray_frame": frame_ids.repeat_interleave(per)}
-            if self.pix_warping:
-                win.update({"c2ws": torch.stack([views[f][1] for f in window]).float().contiguous(),
-                            "table": FrameTable([self.images[f] for f in window], channels_first=True),
-                            "value": torch.zeros((), device=self.device), "first": None})
-            return win
+            views = {f: (known[f] if f in known else fetch(f)) for f in window}
+        window = [f for f in window if views[f] is not None]
+        return window, {f: views[f] for f in window}
 
     def _window_rays(self, win, pix, rq=None):
         """the rays of one iteration over the window: frame f's slice of `pix` through its own view, depth and image
@@ -773,7 +767,7 @@ class SequenceRunner:
         if rmaps is not None:
             radius = rmaps[0][jj, ii]
         elif self.npc.use_dynamic_radius:
-            radius = torch.full_like(d, 0.5 * (self.npc.radius_add + self.npc.radius_query))
+            radius = torch.full_like(d, self._const_radius())
         else:
             radius = None
         return self.npc.add_neural_points(ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous(), d,
@@ -858,75 +852,33 @@ class SequenceRunner:
             for o in range(int(outer_iters)):
                 window, per = first_window if o == 0 else final_refine_window(
                     self.mapped, self.skipped, int(v.counter.value), self.map_rays, self.gen, pix_warping=pix_warping)
-                with torch.no_grad():
-                    if self.render_depth is not None:
-                        self._render_views = {}
-                        views = {f: self._render_view(f) for f in window}
-                        window = [f for f in window if views[f] is not None]     # (per stays, mapper.py:564, :584)
-                        views = {f: views[f] for f in window}
-                    else:
-                        views = {f: self._keyframe_view(f) for f in window}
-                    if not window:
-                        raise ValueError("final refinement: every window frame was skipped")
-                    warp_on = (self.pix_warping if pix_warping is None else bool(pix_warping)) \
-                        and len(window) <= MAX_WARP_FRAMES
-                    rq = [self._radius_maps(f, views[f], add=False)[1] for f in window] if self.color_grad else None
-                    const_r = 0.5 * (npc.radius_add + npc.radius_query) if (rq is None and npc.use_dynamic_radius) else None
-                    c2ws = torch.stack([views[f][1] for f in window]).float().contiguous()
-                    table = WindowTable([views[f][0] for f in window], [self.images[f] for f in window], c2ws, rq,
-                                        channels_first=True)
-                    frame_ids = torch.tensor(window, dtype=torch.int64).to(self.device)
-                    win = {"window": window, "views": views, "per": per, "frame_ids": frame_ids, "table": table}
-                    warp = None
-                    if warp_on:
-                        warp = {"c2ws": table.c2ws, "frame_ids": frame_ids, "ray_frame": frame_ids.repeat_interleave(per),
-                                "table": FrameTable(table.images, channels_first=True),
-                                "value": torch.zeros((), device=self.device), "first": None}
-                    # every iteration's draw in one transfer: [iteration][ii | jj][frame-major rays]
-                    n_rays = per * len(window)
-                    draws = torch.stack([torch.randint(0, v.wd, (n_it, n_rays), generator=self.gen),
-                                         torch.randint(0, v.ht, (n_it, n_rays), generator=self.gen)], 1).to(self.device)
-                    all_depth = bool(torch.stack([(views[f][0] > 0).all() for f in window]).all())
-                geo = npc.geo_feats.detach().clone().requires_grad_(True)
-                col_f = npc.col_feats.detach().clone().requires_grad_(True)
-                opt = FeatureAdam([{"params": [geo], "lr": 0.005}, {"params": [col_f], "lr": 0.005}])
-                self.last_optimizer = opt
-                first = last = None
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                ren.assume_depth = all_depth
-                try:
-                    for it in range(n_it):
-                        pix = draws[it]
-                        with torch.no_grad():
-                            ro, rd, d, gt_col, radius = window_rays(table, pix[0], pix[1], per, ren.fx, ren.fy, ren.cx,
-                                                                    ren.cy, const_radius=const_r)
-                        opt.zero_grad()
-                        loss, depth, colour, seen = self._mapping_loss(ro, rd, d, gt_col, radius, geo, col_f, warp)
-                        if self.map_probe is not None:
-                            self.map_probe(window[-1], dict(ro=ro, rd=rd, d=d, gt_col=gt_col, depth=depth.detach(),
-                                                            colour=colour.detach(), seen=seen, loss=loss.detach(),
-                                                            warp=warp, window=win, frustum=None, radius=radius, pix=pix,
-                                                            refine=o))
-                        loss.backward()
-                        opt.step()
-                        last = loss.detach()
-                        if first is None:
-                            first = last
-                finally:
-                    ren.assume_depth = False
-                torch.cuda.synchronize()
-                elapsed += time.perf_counter() - t0
+                if self.render_depth is not None:
+                    self._render_views = {}
+                window, views = self._window_views(window)                       # (per stays, mapper.py:564, :584)
+                if not window:
+                    raise ValueError("final refinement: every window frame was skipped")
+                warp_on = (self.pix_warping if pix_warping is None else bool(pix_warping)) \
+                    and len(window) <= MAX_WARP_FRAMES
+                s = self._map_setup(None, final=(window, views, per, warp_on), table=True)
+                # every iteration's draw in one transfer: [iteration][ii | jj][frame-major rays]
+                n_rays = per * len(window)
+                draws = torch.stack([torch.randint(0, v.wd, (n_it, n_rays), generator=self.gen),
+                                     torch.randint(0, v.ht, (n_it, n_rays), generator=self.gen)], 1).to(self.device)
+                opt = FeatureAdam([{"params": [s.geo], "lr": 0.005}, {"params": [s.col_f], "lr": 0.005}])
+
+                def rays(it):
+                    pix = draws[it]
+                    return window_rays(s.table, pix[0], pix[1], per, ren.fx, ren.fy, ren.cx, ren.cy,
+                                       const_radius=s.const_r), {}, dict(pix=pix)
+
+                dt, losses = self._train(s, n_it, opt, rays, self._all_depth(s), window[-1], probe_extra=dict(refine=o))
+                elapsed += dt
                 steps += n_it
-                with torch.no_grad():
-                    npc.update_geo_feats(geo.detach())
-                    npc.update_col_feats(col_f.detach())
-                nan = float("nan")
-                self.refine_losses.append((float(first), float(last)) if n_it else (nan, nan))
+                self.refine_losses.append(losses)
                 self.refine_windows.append(list(window))
                 sizes.append(len(window))
                 pers.append(per)
-                warped.append(warp is not None)
+                warped.append(s.warp is not None)
         finally:
             for p, req in frozen:
                 p.requires_grad_(req)
@@ -1073,8 +1025,6 @@ def synthetic_runner(device, K, zero_flow_head=True, map_iters=20, map_rays=1000
     guess of a new keyframe = its generating pose and disparity.  zero_flow_head: the last layer of the flow head is
     zeroed, which makes the generating trajectory a fixed point of the tracking loop (there are no trained weights
     here).  -> (runner, dict(poses, disps, cfg, video, npc, intrinsics))"""
-    import types
-
     import numpy as np
 
     from . import synth
@@ -1127,8 +1077,6 @@ def synthetic_long_runner(device, n_frames=220, leg=60, repeat_every=9, map_iter
     predecessor (zero induced flow: the frontend's redundancy test culls it, rm_keyframe shifts the buffers), loop closure
     enabled, a global BA every `ba_every` keyframes, `map_iters` mapping iterations per kept keyframe, a 512-frame buffer.
     Flow head zeroed: the generating trajectory is a fixed point.  -> (runner, dict(...), frames iterator factory)"""
-    import types
-
     import numpy as np
 
     from . import synth
